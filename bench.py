@@ -17,29 +17,41 @@ header ">syn_<g>", seed 20260101+g, generated directly in HBM by kf_synth_fasta)
 A step = one pass of the device counter over the rank's resident genomes: one
 `kf_count_batch` call (k=7) per sub-batch as the CLI makes it, i.e. zeroing the
 [genomes x 8192] count matrix and the count kernel.
-The default run also times k=11 (BASELINE configs[4]) on the same batch and
+A plain run does only what the headline needs: it generates the batch, streams
+it for the clocks to settle ("prewarm"), runs --warmup untimed and --steps timed
+steps, writes the last step's outputs if --dump-outputs DIR is given, and prints
+the JSON line ("parity": "unchecked").  Everything else below -- the oracle
+checks behind "parity", `roofline.cold_kernel_ms`, "secondary", "by_k", "e2e",
+"sparse" and "cpu_baseline" -- runs only with --full.
+--dump-outputs DIR writes what the last timed step returned to its caller, the
+count matrix and the totals of this rank's genomes, as DIR/counts.npy [rows x
+bins], DIR/totals.npy [rows] and DIR/genome_ids.npy [rows] (float32 while every
+value is below 2^24, else float64; at most 60 MB in all: a seeded sample of the
+rows when the matrix is larger; `_rank<r>` before .npy when N > 1).  The inputs
+are seeded, so two builds run with the same arguments compare file for file.
+With --full the run also times k=11 (BASELINE configs[4]) on the same batch and
 reports it under "secondary"; `roofline.traffic` is the measured HBM bytes per
 launch (rocprofv3 PMC, tools/pmc_traffic.py) when profiles/ holds it.
 `value` = all ranks' sequence characters / max-over-ranks wall time of K steps.
 `roofline.achieved` = algorithmic bytes per launch (FASTA bytes read + 4 B x
 bins written) / the count kernel's average duration,
 timed with HIP events on the launch stream inside the timed region.
-`roofline.cold_kernel_ms` is one launch after the GPU has idled for a second
+`roofline.cold_kernel_ms` (--full) is one launch after the GPU has idled for a second
 (what a CLI batch that follows host I/O sees), measured after the timed region.
-The CPU baseline (rank 0, N=1) times the oracle's C restatement (kind "port":
+The CPU baseline (--full, rank 0, N=1) times the oracle's C restatement (kind "port":
 Jellyfish is not installed) on a bounded sample of the same genomes, OpenMP
 over (genome, ~1 MiB part) pairs on every host CPU this process may use
 (sched_getaffinity, capped by a cgroup CPU quota if one is set).
-`e2e` (rank 0, N=1) is the get_frequencies CLI end to end on 64 bacterial-like
+`e2e` (--full, rank 0, N=1) is the get_frequencies CLI end to end on 64 bacterial-like
 ~5 Mbp genome files in tmpfs (BASELINE configs[2] shape): the pipelined CLI
 wall time, and the same work run stage by stage (file read, H2D + the FASTA
 record index on the device, count, D2H, format + write) to show where the time
 goes.
-`sparse` (rank 0, N=1) is get_kmers' sparse counter (k=31 by default: the
+`sparse` (--full, rank 0, N=1) is get_kmers' sparse counter (k=31 by default: the
 present canonical k-mers per genome by a device radix sort) on 64 of the
 synthetic genomes, genome 0 checked against the oracle.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--k 7]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--k 7] [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...,
    or plain `python bench.py --gpus N`: the process then starts N ranks itself,
    one per GPU, before it touches the GPU, and relays rank 0's line)
@@ -73,6 +85,11 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--k", type=int, default=7)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every check and secondary measurement: the oracle checks (parity), the cold "
+                         "launch, --secondary-k, --by-k, e2e, sparse and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (counts, totals) to DIR/*.npy")
     ap.add_argument("--workload", choices=["auto", "configs1", "configs3"], default="auto",
                     help="auto: configs1 (1,000 genomes per GPU) at N=1, configs3 (50,000 genomes sharded) at N>1")
     ap.add_argument("--genomes-per-gpu", type=int, default=1000, help="configs1 batch per GPU")
@@ -84,18 +101,18 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-sample-genomes", type=int, default=64)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every usable host CPU")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--secondary-k", type=int, default=11,
-                    help="also time this k on the same batch (BASELINE configs[4]); 0 = off; N=1 only")
+                    help="--full: also time this k on the same batch (BASELINE configs[4]); 0 = off; N=1 only")
     ap.add_argument("--by-k", default="3-12",
-                    help="also time every k of this range on the batch (N=1; '' = off): the reference's vocab "
+                    help="--full: also time every k of this range on the batch (N=1; '' = off): the reference's vocab "
                          "branches k=3..10 (main.py:281-296) plus 11 and 12")
     ap.add_argument("--by-k-steps", type=int, default=5)
     ap.add_argument("--by-k-warmup", type=int, default=3)
-    ap.add_argument("--verify", type=int, default=4, help="genomes per rank checked bit-exactly against the oracle")
-    ap.add_argument("--e2e-genomes", type=int, default=64, help="CLI end-to-end files (0 = off; N=1 only)")
+    ap.add_argument("--verify", type=int, default=4, help="--full: genomes per rank checked bit-exactly against the oracle")
+    ap.add_argument("--e2e-genomes", type=int, default=64, help="--full: CLI end-to-end files (0 = off; N=1 only)")
     ap.add_argument("--e2e-len", type=int, default=5_000_000)
-    ap.add_argument("--sparse-k", type=int, default=31, help="get_kmers sparse counter line (0 = off; N=1 only)")
+    ap.add_argument("--sparse-k", type=int, default=31, help="--full: get_kmers sparse counter line (0 = off; N=1 only)")
     ap.add_argument("--sparse-genomes", type=int, default=64)
     return ap.parse_args(argv)
 
@@ -214,6 +231,56 @@ def load_traffic(k: int, workload_tag: str):
         if t.get("k") == k and t.get("workload") == workload_tag:
             return int(t["traffic_bytes"]), os.path.relpath(f, ROOT)
     return None, None
+
+
+DUMP_BUDGET = 60_000_000          # bytes of .npy data per run (--dump-outputs), all ranks together
+
+
+class OutputDump:
+    """--dump-outputs: what the last timed step handed back, the count rows and
+    totals of this rank's genomes, as float .npy files.  The rows are every
+    genome of the rank, or, when they would pass the rank's share of
+    DUMP_BUDGET, a sample of them drawn with a fixed seed (the same rows from
+    run to run).  float32 holds every value exactly while seq_len < 2^24 (no
+    count passes the number of windows); float64 above."""
+
+    def __init__(self, out_dir: str, W, nbins: int):
+        self.dir, self.W = out_dir, W
+        self.dtype = np.float32 if W.args.seq_len < (1 << 24) else np.float64
+        row_bytes = (nbins + 1) * np.dtype(self.dtype).itemsize + 8
+        m = min(W.n, max(1, (DUMP_BUDGET // W.world) // row_bytes))
+        self.rows = (np.arange(W.n) if m == W.n else
+                     np.sort(np.random.default_rng(SEED).choice(W.n, m, replace=False)))
+        self.first = np.cumsum([0] + [c for _, _, c in W.plan])     # sub-batch j holds rows first[j]..first[j+1]
+        self.parts = {}
+
+    def add(self, j: int, out) -> None:
+        """Copy the sampled rows of sub-batch j's (counts, totals) to the host."""
+        if out is None:
+            return
+        torch = self.W.torch
+        a, st, _ = self.W.plan[j]
+        r = self.rows[(self.rows >= self.first[j]) & (self.rows < self.first[j + 1])] - self.first[j]
+        idx = torch.from_numpy(r).to(out[0].device)
+        cnt = out[0].index_select(0, idx).cpu().numpy().view(np.uint32).astype(self.dtype)
+        tot = out[1].index_select(0, idx).cpu().numpy().astype(self.dtype)
+        self.parts[j] = (cnt, tot, (a + r * st).astype(np.float64))
+
+    def write(self) -> dict:
+        os.makedirs(self.dir, exist_ok=True)
+        ign = os.path.join(self.dir, ".gitignore")
+        if not os.path.exists(ign):      # the dump is a run's product wherever DIR lies
+            with open(ign, "w") as f:
+                f.write("*\n")
+        tag = f"_rank{self.W.rank}" if self.W.world > 1 else ""
+        files = {}
+        if not self.parts:               # a rank without genomes
+            return {"dir": self.dir, "files": files, "rows": 0, "of": 0}
+        for i, name in enumerate(("counts", "totals", "genome_ids")):
+            arr = np.concatenate([self.parts[j][i] for j in sorted(self.parts)])
+            np.save(os.path.join(self.dir, f"{name}{tag}.npy"), arr)
+            files[f"{name}{tag}.npy"] = [str(arr.dtype), list(arr.shape)]
+        return {"dir": self.dir, "files": files, "rows": int(len(self.rows)), "of": int(self.W.n)}
 
 
 class Workload:
@@ -340,12 +407,15 @@ class Workload:
                 ok &= bool((cnp[i] == cc).all()) and int(outs[0][1][i]) == t
         return ok
 
-    def measure(self, k, steps, warmup, resident, picks, picks_rest=0, keep=False, pre=None):
+    def measure(self, k, steps, warmup, resident, picks, picks_rest=0, keep=False, pre=None, check=True,
+                dump=None):
         """The timed passes at k over this rank's plan: resident (every sub-batch in
         HBM, one step = all of them) or streamed (each sub-batch generated, timed on
         its own, the times added).  `picks` genomes of the first sub-batch and
         `picks_rest` of every other one are checked against the oracle; `pre` (see
-        run) before the first timed pass.  Returns a dict with the wall time,
+        run) before the first timed pass.  check=False skips every check (a plain
+        bench run); `dump` (an OutputDump) takes the last step's outputs of every
+        sub-batch.  Returns a dict with the wall time,
         per-launch ms, the parity verdict of this rank, and (keep=True, resident)
         the batches."""
         res = {"ok": True, "launch_ms": [], "warm_ms": [], "el": 0.0, "dbs": None, "kc": None, "outs": None}
@@ -353,7 +423,10 @@ class Workload:
             dbs = [self.gen(j) for j in range(len(self.plan))]
             kc, outs, el, ms, wms = self.run(k, steps, warmup, dbs, pre)
             for j in range(len(self.plan)):
-                res["ok"] &= self.verify(k, j, [outs[j]], picks if j == 0 else picks_rest)
+                if check:
+                    res["ok"] &= self.verify(k, j, [outs[j]], picks if j == 0 else picks_rest)
+                if dump is not None:
+                    dump.add(j, outs[j])
             res.update(el=el, launch_ms=ms, warm_ms=wms, kc=kc, dbs=dbs if keep else None,
                        outs=outs if keep else None)
             del outs
@@ -364,7 +437,10 @@ class Workload:
                 res["el"] += e
                 res["launch_ms"] += ms
                 res["warm_ms"] += wms
-                res["ok"] &= self.verify(k, j, outs, picks if j == 0 else picks_rest)
+                if check:
+                    res["ok"] &= self.verify(k, j, outs, picks if j == 0 else picks_rest)
+                if dump is not None:
+                    dump.add(j, outs[0])
                 res["kc"] = kc
                 del outs, db
         return res
@@ -741,7 +817,8 @@ def main() -> None:
     from kf2vecfsw_amd import _native as N
 
     W = Workload(args, dev, rank, world, dist if world > 1 else None, rehearse)
-    kmax = max(args.k, args.secondary_k if (world == 1 and args.secondary_k) else 0)
+    full = args.full
+    kmax = max(args.k, args.secondary_k if (full and world == 1 and args.secondary_k) else 0)
     resident = W.fits(kmax)
     stream = W.stream
     bases = W.n * args.seq_len
@@ -759,14 +836,17 @@ def main() -> None:
         if db0 is not None:
             ceiling.update(stream_ceiling(torch, db0.data, stream, reps=60))
 
-    m = W.measure(args.k, args.steps, args.warmup, resident, args.verify, keep=True, pre=prewarm)
+    dump = OutputDump(args.dump_outputs, W, W.C.num_bins(args.k)) if args.dump_outputs else None
+    m = W.measure(args.k, args.steps, args.warmup, resident, args.verify, keep=True, pre=prewarm, check=full,
+                  dump=dump)
+    dumped = dump.write() if dump is not None else None
     ok = m["ok"]
     kc, dbs = m["kc"], m["dbs"]
     kern_ms = float(np.mean(m["launch_ms"])) if m["launch_ms"] else 0.0
     el, kern_ms = W.max_over_ranks(m["el"], kern_ms)
     ok = W.all_ok(ok)
     first = dbs[0] if dbs else None
-    cold = cold_launch_ms(torch, kc, first, stream) if (rank == 0 and first is not None) else None
+    cold = cold_launch_ms(torch, kc, first, stream) if (full and rank == 0 and first is not None) else None
     nsb = W.nsb
     n = W.n
     # per launch (one sub-batch): FASTA bytes read + 4 B x bins written
@@ -821,7 +901,9 @@ def main() -> None:
                     "batch (~70 ms of HBM streaming; clocks settle over the first ~20-30 ms of sustained load, "
                     "profiles/r04/v1_cold.json)".format(ceiling.get("probe_reps"), ceiling.get("copy_reps"))
                     if ceiling else None),
-        "parity": "ok" if ok else "MISMATCH",
+        "parity": ("ok" if ok else "MISMATCH") if full else "unchecked",
+        "full": full,
+        "outputs": dumped,
         "build_id": N.build_id(),
         "ranks": {"world_size_reported": dist.get_world_size() if world > 1 else 1,
                   "backend": (dist.get_backend() if world > 1 else None),
@@ -833,7 +915,7 @@ def main() -> None:
     if out["ranks"]["world_size_reported"] != world:
         ok = False
         out["parity"] = "MISMATCH"
-    if args.secondary_k and world == 1 and args.secondary_k != args.k and resident:
+    if full and args.secondary_k and world == 1 and args.secondary_k != args.k and resident:
         k2 = args.secondary_k
         st2 = max(3, args.steps // 4)
         kc2, o2, el2, ms2, _ = W.run(k2, st2, 1, dbs)
@@ -853,21 +935,21 @@ def main() -> None:
             "parity": "ok" if ok2 else "MISMATCH"}
         out["parity"] = "ok" if ok else "MISMATCH"
         del o2
-    if args.by_k and world == 1 and resident:
+    if full and args.by_k and world == 1 and resident:
         out["by_k"] = by_k_bench(W, dbs, args, workload_tag)
         ok &= all(v["parity"] == "ok" for v in out["by_k"].values())
         out["parity"] = "ok" if ok else "MISMATCH"
     del dbs, first, m
-    if rank == 0 and world == 1 and args.e2e_genomes:
+    if full and rank == 0 and world == 1 and args.e2e_genomes:
         torch.cuda.empty_cache()
         out["e2e"] = e2e_bench(args, dev)
         ok &= out["e2e"]["parity"] == "ok"
         out["parity"] = "ok" if ok else "MISMATCH"
-    if rank == 0 and world == 1 and args.sparse_k:
+    if full and rank == 0 and world == 1 and args.sparse_k:
         out["sparse"] = sparse_bench(args, dev)
         ok &= out["sparse"]["parity"] == "ok"
         out["parity"] = "ok" if ok else "MISMATCH"
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         ids = [a + i * st for a, st, c in W.plan for i in range(c)]
         out["cpu_baseline"] = cpu_baseline(args, ids)
     if rank == 0:

@@ -71,7 +71,7 @@ def test_bench_gpus2_spawns_two_ranks():
     over gloo under KF_BENCH_REHEARSE=1 on a one-GPU box) over the configs[3]
     batch shape (64 genomes sharded g mod 2), parity ok, n_gpus 2, world size 2
     as torch.distributed reports it."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--total-genomes", "64",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--total-genomes", "64",
            "--sub-batch", "16", "--seq-len", "300000", "--steps", "2", "--warmup", "1", "--no-cpu",
            "--e2e-genomes", "0", "--sparse-k", "0"]
     p = subprocess.run(cmd, env=_env(KF_BENCH_REHEARSE="1"), capture_output=True, text=True, timeout=600)
@@ -83,6 +83,62 @@ def test_bench_gpus2_spawns_two_ranks():
     assert out["ranks"]["launcher"].startswith("bench.py --gpus")
     assert "BASELINE configs[3]" in out["config"]["workload"] and out["config"]["global_batch"] == 64
     assert out["parity"] == "ok"
+
+
+def test_output_dump_rows_are_a_fixed_sample():
+    """--dump-outputs keeps every row while they fit the budget, else the same
+    seeded sample of rows in every run; float32 only while seq_len < 2^24."""
+    import types
+
+    import numpy as np
+    import bench
+
+    def mk(n, seq_len, world=1):
+        W = types.SimpleNamespace(args=types.SimpleNamespace(seq_len=seq_len), n=n, world=world, rank=0,
+                                  plan=[(0, world, n)])
+        return bench.OutputDump("unused", W, 8192)
+
+    d = mk(1000, 5_000_000)
+    assert d.dtype == np.float32 and np.array_equal(d.rows, np.arange(1000))
+    a, b = mk(5000, 5_000_000), mk(5000, 5_000_000)
+    assert np.array_equal(a.rows, b.rows) and 0 < len(a.rows) < 5000 and (np.diff(a.rows) > 0).all()
+    assert len(a.rows) * (8193 * 4 + 8) <= bench.DUMP_BUDGET
+    assert len(mk(5000, 5_000_000, world=2).rows) * 2 * (8193 * 4 + 8) <= bench.DUMP_BUDGET
+    assert mk(10, 1 << 24).dtype == np.float64
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step_outputs(oracle, tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) times the steps it is asked for,
+    prints the headline keys and none of the --full legs, and --dump-outputs
+    writes the last step's count rows and totals: equal to the oracle's on the
+    same seeded genomes (so the same from run to run)."""
+    import numpy as np
+    from bench import SEED
+    L, n, k = 200_000, 5, 7
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--genomes-per-gpu", str(n), "--seq-len", str(L), "--dump-outputs", str(d)]
+    p = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and len(out["roofline"]["warmup_kernel_ms"]) == 1
+    assert out["ms_per_step"] > 0 and out["unit"] == "Gbases/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "u32" and out["value"] == pytest.approx(n * L / out["ms_per_step"] / 1e6, rel=1e-2)
+    assert out["parity"] == "unchecked" and out["full"] is False
+    assert not {"secondary", "by_k", "e2e", "sparse", "cpu_baseline"} & set(out)
+    assert out["roofline"]["cold_kernel_ms"] is None
+    got = {f.name: np.load(f) for f in d.glob("*.npy")}
+    assert sorted(got) == ["counts.npy", "genome_ids.npy", "totals.npy"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64_000_000
+    assert np.array_equal(got["genome_ids.npy"], np.arange(n))
+    for g in range(n):
+        c, t = oracle.count(oracle.synth_genome(g, SEED + g, L, 80), k)
+        assert np.array_equal(got["counts.npy"][g], c.astype(np.float32)), g
+        assert got["totals.npy"][g] == t == L - k + 1
 
 
 @pytest.mark.gpu

@@ -4,7 +4,7 @@
 # Steps (each under its own time limit; the first failure ends the session):
 #   tests[=EXPR]  pytest tests -m gpu [-k EXPR]        -> gpurun_out/TAG/pytest_gpu.log
 #   smoke         __graft_entry__.smoke()              -> smoke.log
-#   bench         the driver's bench command (--steps 20 --warmup 5)  -> bench.json
+#   bench         bench.py --full --gpus 1 --steps 20 --warmup 5 (every leg)  -> bench.json
 #   benchonly     bench without e2e / sparse / cpu legs -> benchonly.json
 #   prof          rocprofv3 --kernel-trace --stats of `benchonly` (k=7 + k=11 only,
 #                 so the per-kernel averages are the timed launches)  -> prof/
@@ -29,7 +29,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$REPO"
-BENCH_ONLY="--steps 20 --warmup 5 --no-cpu --e2e-genomes 0 --sparse-k 0"
+BENCH_ONLY="--full --steps 20 --warmup 5 --no-cpu --e2e-genomes 0 --sparse-k 0"
 n=0
 run() {   # run LIMIT OUTFILE CMD...
   local lim=$1 out=$2; shift 2
@@ -45,7 +45,7 @@ for step in "$@"; do
     tests) run 1100 "$OUT/pytest_gpu.log" python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
     tests=*) run 1100 "$OUT/pytest_gpu_$n.log" python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "${step#tests=}" ;;
     smoke) run 300 "$OUT/smoke.log" python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run 500 "$OUT/bench.json" python -u bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    bench) run 500 "$OUT/bench.json" python -u bench.py --full --gpus 1 --steps 20 --warmup 5 ;;
     benchonly) run 300 "$OUT/benchonly.json" python -u bench.py $BENCH_ONLY ;;
     prof) (cd /tmp && export TMPDIR=/tmp && run 400 "$OUT/prof_bench.json" rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run -f csv -- python3 "$REPO/bench.py" $BENCH_ONLY) || exit 1 ;;
     profsparse) (cd /tmp && export TMPDIR=/tmp && run 400 "$OUT/profsparse.json" rocprofv3 --kernel-trace --stats -d "$OUT/profsparse" -o run -f csv -- python3 "$REPO/tools/sparse_bench.py" --genomes 64 --k 13,16,21,31 --reps 3) || exit 1 ;;

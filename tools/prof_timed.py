@@ -1,5 +1,5 @@
 """The bench's timed k1x_kernel<7> / bucket_kernel<11> dispatches out of a
-rocprofv3 --kernel-trace run of `bench.py --gpus 1 --steps S --warmup W`.
+rocprofv3 --kernel-trace run of `bench.py --full --gpus 1 --steps S --warmup W`.
 
 The summary's per-kernel average mixes in the e2e CLI's small launches; the
 configs[1] launches are the ones over 0.5 ms (k=7) in order: W warm-up, S timed,
@@ -41,7 +41,7 @@ def main():
     k11 = [m for _, m in sorted(k11)]
     W, S = a.warmup, a.steps
     out = {
-        "command": f"rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps {S} --warmup {W}",
+        "command": f"rocprofv3 --kernel-trace --stats -- python3 bench.py --full --gpus 1 --steps {S} --warmup {W}",
         "k1x_kernel<7> dispatches on the configs[1] batch (>0.5 ms), in order": [round(x, 4) for x in k7],
         "warmup_ms": [round(x, 4) for x in k7[:W]],
         "timed_mean_ms": round(sum(k7[W:W + S]) / max(1, len(k7[W:W + S])), 4),
