@@ -20,7 +20,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES_HIP = ["kf_count.hip", "kf_bucket.hip", "kf_chunks.hip", "kf_sparse.hip", "kf_index.hip"]
 SOURCES_CPP = ["kf_host.cpp"]
-DEPS = SOURCES_HIP + SOURCES_CPP + ["kf_internal.h", "kf_front.h", "../../include/kf2vec_gpu.h"]
+DEPS = SOURCES_HIP + SOURCES_CPP + ["kf_internal.h", "kf_front.h", "kf_scan.h", "../../include/kf2vec_gpu.h"]
 
 
 def source_id() -> str:
@@ -56,9 +56,9 @@ def _stale() -> bool:
 
 def build(force: bool = False, verbose: bool = False, ablation: bool = False, out: str | None = None) -> str:
     """ablation=True: a profiling build of the product (KF_PROFILE_BUILD: the
-    bucket kernels' KF_BUCKET_PROFILE / KF_BK_WEIGHTS knobs, KF_K9_BUCKET) from
-    the sources with tools/zoo/bucket_ablations.patch applied (KF_BK_ABL=n via
-    KF_HIPCC_FLAGS).
+    KF_BUCKET_PROFILE, KF_SPARSE_PROFILE and KF_SPARSE_DEBUG environment hooks)
+    from the sources with tools/zoo/bucket_ablations.patch applied (KF_BK_ABL=n
+    via KF_HIPCC_FLAGS).
     Serialised by a file lock: every rank of a multi-process run may call it."""
     import fcntl
     out = out or OUT
@@ -72,7 +72,7 @@ def build(force: bool = False, verbose: bool = False, ablation: bool = False, ou
         return _build_locked(verbose, ablation, out)
 
 
-HEADERS = ["kf_internal.h", "kf_front.h", "../../include/kf2vec_gpu.h"]
+HEADERS = ["kf_internal.h", "kf_front.h", "kf_scan.h", "../../include/kf2vec_gpu.h"]
 
 _TOOLCHAIN: list[bytes] = []
 

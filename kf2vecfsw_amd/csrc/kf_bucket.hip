@@ -1,7 +1,7 @@
 // kf_bucket.hip -- canonical k-mer counting for large k (4^k bins beyond LDS).
 //
 // Reference path: kf2vec/main.py:309-323 (`jellyfish count -C -m k` + dump), the
-// same as kf_count.hip; this file serves k >= kBucketMinK, where one genome's
+// same as kf_count.hip; this file serves k >= 10, where one genome's
 // canonical bins (2,097,152 at k=11) do not fit a 160 KiB LDS and per-k-mer
 // global atomics run at ~25 G/s (measured), far below the byte stream.
 //
@@ -35,107 +35,44 @@ namespace kf {
 
 // (The profiling ablations of rounds 3-5 -- wrong counts by design -- live in
 // tools/zoo/bucket_ablations.patch, applied by `python -m kf2vecfsw_amd.build
-// --ablation`; DESIGN.md section 4 lists them.)
-// Phase 2 record groups: 1 = two groups of 4 windows alternate (the next one in
-// flight while one is counted), 0 = one group of 8 windows (a bucket's further
-// groups wait for their loads).
-#ifndef KF_BK_DB
-#define KF_BK_DB 1
-#endif
-// With KF_BK_DB, k <= 10: both groups of the next bucket are issued before the
-// current bucket's flush, so its first two groups never wait for loads issued
-// after the flush (one process: k=9 6.10 -> 5.83 ms, k=10 6.71 -> 6.52).  k >= 11
-// issues one: k=11 buckets need ~1.2 groups per wave (8.69 vs 8.73 ms) and k=12
-// ~0.3 (18.9 vs 19.2), so a second group is mostly empty loads.
-#ifndef KF_BK_PRE2
-#define KF_BK_PRE2 1
-#endif
-// Non-temporal stores for the record copy-out and the count rows: k=11 9.61 ->
-// 8.97 ms, k=9 unchanged (one process, profiles/r03/v10_lib_ab_k*_nt_stores.json).
-#ifndef KF_NT_STORES
-#define KF_NT_STORES 1
-#endif
-// Staggered phases (see the piece loop) for k >= KF_BK_LAG (0: never): half of
-// the workgroups run one phase behind the others, with two record slots per
-// workgroup.  One process (profiles/r03/v18_lib_ab_k*_lag.json): k=10 6.55 ->
-// 6.50 ms, k=11 8.71 -> 8.46, k=12 18.67 -> 18.26; k=9 5.69 -> 5.92 (off).
-#ifndef KF_BK_LAG
-#define KF_BK_LAG 10
-#endif
-#ifndef KF_BK_LAG_SHIFT   // lagged workgroups: bit KF_BK_LAG_SHIFT of blockIdx.x (3: half of each XCD)
-#define KF_BK_LAG_SHIFT 3
-#endif
-#ifndef KF_BK_PRE2_MAXK   // KF_BK_PRE2 applies to k <= this
-#define KF_BK_PRE2_MAXK 10
-#endif
-// Phase-2 rounds per wave: 0 = dealt round-robin (round wave + W j); otherwise a
-// contiguous block of rounds per wave, its size proportional to byte (wave >> 2)
-// of KF_BK_RW (the wave's age slot on its SIMD, as K1x's KF_WAVE_WEIGHTS): the
-// SIMD issues its oldest wave first, so equal shares leave the older waves
-// waiting at every bucket barrier for the youngest.
-#ifndef KF_BK_RW
-#define KF_BK_RW 0x060B1114   // (20, 17, 11, 6): k=11 8.35 -> 8.17 ms, k=9 unchanged (profiles/r04/v6_lib_ab_k*_rw_dup.json)
-#endif
-constexpr uint32_t kBkSlots = KF_BK_LAG ? 2u : 1u;   // record / meta / roff slots per workgroup
-// Wave priority by age slot (tools/ A/B builds): bit 0 = phase 1, bit 1 = phase 2
-// run at s_setprio(wave >> 2), so that the youngest wave of each SIMD (which the
-// SIMD issues last) is not the one every barrier waits for.
-#ifndef KF_BK_PRIO
-#define KF_BK_PRIO 0
-#endif
-// Phase-1 staging slots (tools/ A/B builds): 1 = record position p goes to u16
-// slot p with bits 0 and 2 swapped inside its 8-record unit, so the consecutive
-// ranks one ds_add_rtn hands the lanes of a bucket land in different dwords
-// (banks) instead of pairs sharing one; phase 2 counts a unit in any order.
-// Measured and left off (profiles/r05/k11ab_*): phase-1 bank-conflict cycles
-// unchanged (1.050e9 -> 1.066e9 at k = 11: same-dword pairs are not conflicts),
-// VALU instructions +46 %, k = 11 8.59 -> 8.85 ms, k = 9/10/12 slower as well.
-#ifndef KF_BK_SWZ
-#define KF_BK_SWZ 0
-#endif
-__device__ __forceinline__ uint32_t stage_slot(uint32_t p) {
-    if (!KF_BK_SWZ) return p;
-    const uint32_t x = (p ^ (p >> 2)) & 1u;
-    return p ^ (x | (x << 2));
-}
-__device__ __forceinline__ void bk_setprio(uint32_t p) {   // p wave-uniform
-    if (p == 0) __builtin_amdgcn_s_setprio(0);
-    else if (p == 1) __builtin_amdgcn_s_setprio(1);
-    else if (p == 2) __builtin_amdgcn_s_setprio(2);
-    else __builtin_amdgcn_s_setprio(3);
-}
+// --ablation`; DESIGN.md section 4 lists them.  The A/B experiments behind the
+// constants below are in DESIGN.md section 8, "settled build knobs".)
 
-// Workgroup shape (per k, compile time): W = 16 waves, one workgroup per CU,
-// 32768-code buckets (a 128 KiB histogram); or W = 8 waves, two workgroups per
-// CU, 16384-code buckets (64 KiB), so that one workgroup's barrier waits are
-// filled by the other's waves and the two phases of different pieces overlap on
-// one CU.  KF_BK_W<k> (tools/ A/B builds):
-#ifndef KF_BK_W9
-#define KF_BK_W9 16
-#endif
-#ifndef KF_BK_W10
-#define KF_BK_W10 16
-#endif
-#ifndef KF_BK_W11
-#define KF_BK_W11 16
-#endif
-constexpr int bk_w(int K) { return K == 9 ? KF_BK_W9 : K == 10 ? KF_BK_W10 : K == 11 ? KF_BK_W11 : 16; }
-// bytes per piece (one workgroup): a wave range is <= piece / W + 16 bytes, so
-// <= 1017 rounds at W = 8 (<= 128 phase-2 runs per wave, two per lane) and <= 509
-// at W = 16
+// Workgroup shape: 16 waves, one workgroup per CU, 32768-code buckets (a 128 KiB
+// histogram).
+constexpr int kBkWaves = 16;
+constexpr int kBkBits = 15;   // code bits per bucket
+// bytes per piece (one workgroup): a wave range is <= piece / 16 + 16 bytes, so
+// <= 509 rounds (phase-2 runs of one wave: at most one per lane)
 constexpr uint64_t kPieceMax = (8ull << 20) - (64ull << 10);
-template <int W>
-struct BkGeom {
-    static_assert(W == 8 || W == 16, "8 or 16 waves");
-    static constexpr int waves = W;
-    static constexpr int block = W * kWave;
-    static constexpr int bits = W == 16 ? 15 : 14;                        // code bits per bucket
-    static constexpr uint32_t codes = 1u << bits;
-    static constexpr uint32_t round_recs = W * kChunk;                   // windows per round
-    static constexpr uint32_t rmax = (uint32_t)(kPieceMax / round_recs) + 2;   // rounds per piece
-    static constexpr int halves = (rmax + W * kWave - 1) / (W * kWave);   // phase-2 runs per lane
-    static_assert(halves <= 2, "phase-2 run tables hold two runs per lane");
-};
+// Staggered phases (see the piece loop): the workgroups with this bit of
+// blockIdx.x set (3: half of each XCD) run one phase behind the others, with two
+// record slots per workgroup: k=11 8.71 -> 8.46 ms (profiles/r03/v18_lib_ab_k*_lag.json).
+constexpr uint32_t kBkLagShift = 3;
+constexpr uint32_t kBkSlots = 2;   // record / meta / roff slots per workgroup
+// Phase-2 rounds per wave: a contiguous block of rounds, its size proportional
+// to byte (wave >> 2) of kBkRoundWeights (the wave's age slot on its SIMD, as
+// K1x's kWaveWeights): the SIMD issues its oldest wave first, so equal shares
+// leave the older waves waiting at every bucket barrier for the youngest.
+// (20, 17, 11, 6): k=11 8.35 -> 8.17 ms (profiles/r04/v6_lib_ab_k*_rw_dup.json).
+constexpr uint32_t kBkRoundWeights = 0x060B1114;
+// Phase-2 record groups: two groups of kBkGroupWindows windows alternate (the
+// next one in flight while one is counted).
+constexpr int kBkGroupWindows = 4;
+// k <= 10: both groups of the next bucket are issued before the current
+// bucket's flush, so its first two groups never wait for loads issued after the
+// flush (k=10 6.71 -> 6.52 ms).  k >= 11 issues one: its buckets need ~1.2
+// groups per wave (k=12 ~0.3), so a second group is mostly empty loads.
+constexpr bool bk_pre2(int K) { return K <= 10; }
+// Phase-1 rank counters: each bucket's round counter is split into R = 2^rl
+// lane replicas (lane L ranks into replica L mod R), so the 64 lanes of one
+// ds_add_rtn spread over the banks instead of piling onto the few counters of
+// random buckets.  A round's table has nbk x R entries (bucket major), 1 to 8
+// per lane.  log2 R: k = 10 R = 16 7.27 ms (shared counters 7.51;
+// profiles/r03/v5_lib_ab_k*_rank_replicas.json); k >= 11 stays at R = 1 (its
+// tables cost more than the conflicts they remove; profiles/r05/k11ab3_*).
+constexpr uint32_t bk_rl(int K) { return K == 10 ? 4 : 0; }
+
 // A record is the low 16 bits of s: its code in the bucket (s mod codes) plus the
 // bucket's low 16 - bits bits (the same for a whole bucket; phase 1 stores s as
 // it is, one op less per window).  Runs (one bucket, one round) are padded to
@@ -143,47 +80,23 @@ struct BkGeom {
 // (x < 64).  Phase 2 XORs each record with bucket b's high part (b mod
 // 2^(16-bits)) << bits: records become s mod codes, sentinels codes + x, a trash
 // area past the histogram, so a 16-byte unit never needs a range test.
-
-// Phase-1 rank counters: each bucket's round counter is split into R = 2^rl
-// lane replicas (lane L ranks into replica L mod R), so the 64 lanes of one
-// ds_add_rtn spread over the banks instead of piling onto the few counters of
-// random buckets.  A round's table has nbk x R entries (bucket major), 1 to 8
-// per lane.  Measured (tools/lds_rank_rate.hip, cycles per wave-instruction per
-// CU): 8 shared counters 28.7 -> 7.3 with 64 replicas; 32: 13.7 -> 7.3; 128:
-// 11.2 -> 8.7 with 4.  In the kernel (profiles/r03/v5_lib_ab_k*_rank_replicas.json,
-// one process): k = 9 R = 32 6.39 ms (shared counters 9.05), k = 10 R = 16 7.27
-// (7.51); k = 11 stays at R = 1: R = 4 measured 9.59 vs 9.24 in round 3 (its
-// 512-entry tables cost more than the conflicts they remove), and R = 2 leaves
-// phase 1's bank-conflict cycles where they were (1.05e9 -> 1.10e9) and its time
-// too (processes alternated: 8.58 vs 8.58 ms; profiles/r05/k11ab3_*).  log2 R
-// per k (KF_BK_RL<k>, tools/ only):
-#ifndef KF_BK_RL9
-#define KF_BK_RL9 5
-#endif
-#ifndef KF_BK_RL10
-#define KF_BK_RL10 4
-#endif
-#ifndef KF_BK_RL11
-#define KF_BK_RL11 0
-#endif
-#ifndef KF_BK_RL12
-#define KF_BK_RL12 0
-#endif
-constexpr uint32_t bk_rl(int K) {
-    return K == 9 ? KF_BK_RL9 : K == 10 ? KF_BK_RL10 : K == 11 ? KF_BK_RL11 : KF_BK_RL12;
-}
-
-template <int K, int W = bk_w(K)>
-struct Bk : BkGeom<W> {
-    using G = BkGeom<W>;
-    static constexpr uint32_t nbk = (1u << (2 * K)) >> G::bits;   // buckets
-    // (W = 8: twice the buckets, half the replicas: the same counter count)
-    static constexpr uint32_t rl = W == 16 || bk_rl(K) == 0 ? bk_rl(K) : bk_rl(K) - 1;
+template <int K>
+struct Bk {
+    static constexpr int waves = kBkWaves;
+    static constexpr int block = waves * kWave;
+    static constexpr int bits = kBkBits;
+    static constexpr uint32_t codes = 1u << bits;
+    static constexpr uint32_t round_recs = waves * kChunk;                // windows per round
+    static constexpr uint32_t rmax = (uint32_t)(kPieceMax / round_recs) + 2;   // rounds per piece
+    static constexpr int halves = (rmax + block - 1) / block;             // phase-2 runs per lane
+    static_assert(halves <= 2, "phase-2 run tables hold two runs per lane");
+    static constexpr uint32_t nbk = (1u << (2 * K)) >> bits;        // buckets
+    static constexpr uint32_t rl = bk_rl(K);
     static constexpr uint32_t nrep = 1u << rl;                      // rank replicas per bucket
     static constexpr uint32_t nent = nbk << rl;                     // rank entries per round
     static constexpr uint32_t epl = nent / kWave;                   // rank entries per lane
-    static constexpr uint32_t round_cap = G::round_recs + 7 * nbk;  // records of a padded round
-    static constexpr uint64_t rec_cap = (uint64_t)G::rmax * round_cap + 8;   // per workgroup
+    static constexpr uint32_t round_cap = round_recs + 7 * nbk;     // records of a padded round
+    static constexpr uint64_t rec_cap = (uint64_t)rmax * round_cap + 8;   // per workgroup
     // LDS byte layout.  Phase 2: the histogram (codes u32) at 0.  Phase 1 reuses it:
     // two round staging buffers, then one private rank-entry offset table per
     // wave.  After the histogram: three rotating sets of round rank counters
@@ -194,15 +107,15 @@ struct Bk : BkGeom<W> {
     static constexpr uint32_t stage = 0;                            // + (r & 1) * stage_bytes
     static constexpr uint32_t tbl_bytes = nent * 4 + 16;            // per wave (16-byte aligned)
     static constexpr uint32_t rbase = 2 * stage_bytes;              // + wave * tbl_bytes
-    static constexpr uint32_t dirty = rbase + W * tbl_bytes;       // phase-1 footprint in hist
-    static constexpr uint32_t cnt = G::codes * 4;                   // + (r % 3) * nent * 4
-    static constexpr uint32_t red = (cnt + 3 * nent * 4 + 7) & ~7u; // W u64
+    static constexpr uint32_t dirty = rbase + waves * tbl_bytes;    // phase-1 footprint in hist
+    static constexpr uint32_t cnt = codes * 4;                      // + (r % 3) * nent * 4
+    static constexpr uint32_t red = (cnt + 3 * nent * 4 + 7) & ~7u; // waves u64
     static constexpr uint32_t lds_bytes =
-        red + W * 8 > cnt + 256 ? red + W * 8 : cnt + 256;         // trash: 64 bins at cnt
-    static constexpr uint32_t hmask = (1u << (16 - G::bits)) - 1u;  // bucket bits inside a record
+        red + waves * 8 > cnt + 256 ? red + waves * 8 : cnt + 256;  // trash: 64 bins at cnt
+    static constexpr uint32_t hmask = (1u << (16 - bits)) - 1u;     // bucket bits inside a record
     static_assert(epl >= 1 && epl <= 8 && (epl & (epl - 1)) == 0 && nent == epl * kWave, "1-8 entries per lane");
-    static_assert(dirty <= G::codes * 4, "phase-1 tables must fit the histogram area");
-    static_assert(lds_bytes * (16 / W) <= 160 * 1024, "LDS (16 / W workgroups per CU)");
+    static_assert(dirty <= codes * 4, "phase-1 tables must fit the histogram area");
+    static_assert(lds_bytes <= 160 * 1024, "LDS (one workgroup per CU)");
     static_assert(round_cap < 65536, "round offsets are u16");
 };
 
@@ -226,9 +139,6 @@ typedef __attribute__((address_space(3))) uint16_t lds_u16;
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4u lds_v4u;
 
-__device__ __forceinline__ uint32_t lds_add_rtn(uint32_t a, uint32_t v) {
-    return __hip_atomic_fetch_add((lds_u32*)(uintptr_t)a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 __device__ __forceinline__ uint32_t lds_xchg(uint32_t a, uint32_t v) {
     return __hip_atomic_exchange((lds_u32*)(uintptr_t)a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
@@ -283,10 +193,6 @@ __device__ __forceinline__ void lds_stn(uint32_t a, const uint32_t (&v)[N]) {
             *(volatile lds_v4u*)(uintptr_t)(a + 16 * i) = v4u{v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]};
     }
 }
-// Barrier for LDS traffic only: outstanding global loads (the byte-stream
-// prefetch) stay in flight across it.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // Number of pieces of a genome of `len` bytes (an empty genome still gets one:
 // its count row is written by the piece's flush).
 __device__ __forceinline__ uint32_t n_pieces(uint64_t len) {
@@ -403,8 +309,7 @@ bucket_kernel(CountArgs A, BucketArgs B) {
     // slots), so that half of the CUs (every other group of 8 workgroups: half of
     // each XCD) are in the LDS-bound phase 1 while the others stream phase 2's
     // records and rows, instead of all CUs switching phase together.
-    constexpr bool kLagK = KF_BK_LAG && K >= KF_BK_LAG;
-    const uint32_t lag = kLagK ? ((blockIdx.x >> KF_BK_LAG_SHIFT) & 1u) : 0u;
+    const uint32_t lag = (blockIdx.x >> kBkLagShift) & 1u;
     const uint32_t nmine = blockIdx.x < npiece ? (npiece - 1u - blockIdx.x) / gridDim.x + 1u : 0u;
     struct Piece {
         int32_t g;
@@ -433,7 +338,7 @@ bucket_kernel(CountArgs A, BucketArgs B) {
 
     for (uint32_t it = 0; it < nmine + lag; ++it) {
       if (it < nmine) {
-        const uint32_t slot = kLagK ? (it & 1u) : 0u;
+        const uint32_t slot = it & 1u;
         uint16_t* rec = rec_slot(B, (uint64_t)blockIdx.x * kBkSlots + slot, L::rec_cap);
         uint16_t* meta = B.meta + ((uint64_t)blockIdx.x * kBkSlots + slot) * (NBK + 1) * L::rmax;
         uint32_t* roff = B.roff + ((uint64_t)blockIdx.x * kBkSlots + slot) * L::rmax;
@@ -446,7 +351,6 @@ bucket_kernel(CountArgs A, BucketArgs B) {
 
         // ---------------------------------------------------------- phase 1
         const uint64_t t_p1 = B.prof ? __builtin_amdgcn_s_memtime() : 0;
-        if (KF_BK_PRIO) bk_setprio((KF_BK_PRIO & 1) ? (uint32_t)wave >> 2 : 0u);
         Range rg;
         uint32_t nch = 0;
         if (lo < hi) {
@@ -482,11 +386,7 @@ bucket_kernel(CountArgs A, BucketArgs B) {
             const uint32_t st = L::stage + (r & 1) * L::stage_bytes;
             for (uint32_t q = tid; q < T / 8; q += L::block) {
                 const v4u v = *(lds_v4u*)(uintptr_t)(st + 16 * q);
-#if KF_NT_STORES
                 __builtin_nontemporal_store(v, (v4u*)(rec + o + 8 * q));
-#else
-                *(v4u*)(rec + o + 8 * q) = v;
-#endif
             }
         };
         auto round = [&](uint32_t r, uint4& bf) {
@@ -623,7 +523,7 @@ bucket_kernel(CountArgs A, BucketArgs B) {
 #pragma unroll
                     for (uint32_t x = 0; x < 7; ++x)
                         if (x < npad)
-                            *(volatile lds_u16*)(uintptr_t)(st + 2 * stage_slot(e + x)) =
+                            *(volatile lds_u16*)(uintptr_t)(st + 2 * (e + x)) =
                                 (uint16_t)((((bid(q) ^ 1u) & L::hmask) << L::bits) | ((e + x) & 63u));
                 }
             }
@@ -637,10 +537,10 @@ bucket_kernel(CountArgs A, BucketArgs B) {
                 if (s[15] != 0xFFFFFFFFu) rk[15] += lds_ld(rbr + ent_b(s[15]));
 #pragma unroll
                 for (int j = 0; j < 15; ++j) {
-                    *(volatile lds_u16*)(uintptr_t)(st + 2 * stage_slot(rk[j])) = (uint16_t)s[j];
+                    *(volatile lds_u16*)(uintptr_t)(st + 2 * rk[j]) = (uint16_t)s[j];
                 }
                 if (s[15] != 0xFFFFFFFFu)
-                    *(volatile lds_u16*)(uintptr_t)(st + 2 * stage_slot(rk[15])) = (uint16_t)s[15];
+                    *(volatile lds_u16*)(uintptr_t)(st + 2 * rk[15]) = (uint16_t)s[15];
             } else if (have) {
 #pragma unroll
                 for (int j = 0; j < 16; ++j)
@@ -648,7 +548,7 @@ bucket_kernel(CountArgs A, BucketArgs B) {
 #pragma unroll
                 for (int j = 0; j < 16; ++j)
                     if (s[j] != 0xFFFFFFFFu)
-                        *(volatile lds_u16*)(uintptr_t)(st + 2 * stage_slot(rk[j])) = (uint16_t)s[j];
+                        *(volatile lds_u16*)(uintptr_t)(st + 2 * rk[j]) = (uint16_t)s[j];
             }
             t_prev = T;
             off_prev = off;
@@ -670,7 +570,7 @@ bucket_kernel(CountArgs A, BucketArgs B) {
         if (B.prof && lane == 0) B.prof[8 * gridDim.x + 4 * (W * blockIdx.x + wave) + 2] += p1w;
       }
       if (it >= lag) {
-        const uint32_t slot = kLagK ? ((it - lag) & 1u) : 0u;
+        const uint32_t slot = (it - lag) & 1u;
         uint16_t* rec = rec_slot(B, (uint64_t)blockIdx.x * kBkSlots + slot, L::rec_cap);
         uint16_t* meta = B.meta + ((uint64_t)blockIdx.x * kBkSlots + slot) * (NBK + 1) * L::rmax;
         uint32_t* roff = B.roff + ((uint64_t)blockIdx.x * kBkSlots + slot) * L::rmax;
@@ -682,15 +582,14 @@ bucket_kernel(CountArgs A, BucketArgs B) {
         // records and meta were stored by other waves of this workgroup: wait for
         // the stores, and read them with L1-bypassing loads below
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (KF_BK_PRIO) bk_setprio((KF_BK_PRIO & 2) ? (uint32_t)wave >> 2 : 0u);
         const uint64_t t_p2 = B.prof ? __builtin_amdgcn_s_memtime() : 0;
         for (uint32_t i = tid; i < L::dirty / 4; i += L::block) lds_st(L::hist + 4 * i, 0u);   // phase-1 area
         lds_barrier();
         uint32_t* row = A.counts + (uint64_t)g * A.nbins;
         const bool split = np > 1;
         unsigned long long tsum = 0;
-        // Run table of this wave: run j (< nrun) <-> round wave + W j, held by lane
-        // j mod 64 in half j / 64 (W = 8 needs up to 128 runs).  A run is the whole
+        // Run table of this wave: run j (< nrun) <-> round rw0 + j, held by lane
+        // j mod 64 in half j / 64.  A run is the whole
         // units of one bucket in one round (padded by phase 1), and the units of
         // all the wave's runs are laid end to end (prefix P over the runs), so
         // every load instruction carries 64 units whatever the run lengths.  A
@@ -702,21 +601,18 @@ bucket_kernel(CountArgs A, BucketArgs B) {
         bool myr_ok[H];
         uint32_t myr_c[H], ro[H];
         uint32_t nrun = 0;
-        constexpr bool kRw = KF_BK_RW != 0 && W == 16;
-        uint32_t rw0 = 0, rw1 = 0;   // kRw: this wave's rounds [rw0, rw1)
-        if constexpr (kRw) {
-            constexpr uint32_t wts = (uint32_t)KF_BK_RW;
-            constexpr uint32_t w0 = wts & 0xFFu, w1 = (wts >> 8) & 0xFFu, w2 = (wts >> 16) & 0xFFu, w3 = wts >> 24;
-            constexpr uint32_t m01 = w0 > w1 ? w0 : w1, m23 = w2 > w3 ? w2 : w3, mx = m01 > m23 ? m01 : m23;
-            constexpr uint32_t tot = 4u * (w0 + w1 + w2 + w3);
-            static_assert((uint64_t)L::rmax * mx <= (uint64_t)tot * 64u * H - tot, "a wave's rounds must fit its run table");
-            rw0 = (nround * wave_frac((uint32_t)wave, wts)) >> 20;
-            rw1 = (nround * wave_frac((uint32_t)wave + 1, wts)) >> 20;
-        }
+        constexpr uint32_t wts = kBkRoundWeights;
+        constexpr uint32_t w0 = wts & 0xFFu, w1 = (wts >> 8) & 0xFFu, w2 = (wts >> 16) & 0xFFu, w3 = wts >> 24;
+        constexpr uint32_t m01 = w0 > w1 ? w0 : w1, m23 = w2 > w3 ? w2 : w3, mx = m01 > m23 ? m01 : m23;
+        constexpr uint32_t tot = 4u * (w0 + w1 + w2 + w3);
+        static_assert((uint64_t)L::rmax * mx <= (uint64_t)tot * 64u * H - tot, "a wave's rounds must fit its run table");
+        // this wave's rounds [rw0, rw1)
+        const uint32_t rw0 = (nround * wave_frac((uint32_t)wave, wts)) >> 20;
+        const uint32_t rw1 = (nround * wave_frac((uint32_t)wave + 1, wts)) >> 20;
 #pragma unroll
         for (int h = 0; h < H; ++h) {
-            const uint32_t myr = kRw ? rw0 + 64u * h + (uint32_t)lane : (uint32_t)wave + (uint32_t)W * (64u * h + (uint32_t)lane);
-            myr_ok[h] = kRw ? myr < rw1 : myr < nround;
+            const uint32_t myr = rw0 + 64u * h + (uint32_t)lane;
+            myr_ok[h] = myr < rw1;
             myr_c[h] = myr_ok[h] ? myr : 0u;
             nrun += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(myr_ok[h]));
             const uint32_t ro_l = __builtin_nontemporal_load(roff + myr_c[h]);
@@ -759,8 +655,8 @@ bucket_kernel(CountArgs A, BucketArgs B) {
             if (H == 1 || j < 64u) return (uint32_t)__builtin_amdgcn_readlane((int)x[0], (int)j);
             return (uint32_t)__builtin_amdgcn_readlane((int)x[H - 1], (int)(j - 64u));
         };
-        constexpr int kGW = KF_BK_DB ? 4 : 8;
-        constexpr bool kPre2 = KF_BK_PRE2 && K <= KF_BK_PRE2_MAXK;
+        constexpr int kGW = kBkGroupWindows;
+        constexpr bool kPre2 = bk_pre2(K);
         struct Grp {
             v4u v[kGW];
             uint32_t act;   // bit x: this lane's unit of window x exists
@@ -834,11 +730,7 @@ bucket_kernel(CountArgs A, BucketArgs B) {
                 tsum += v[t];
             }
             if (!split && !B.accumulate && g4 >= c0 && g4 + 4 <= c1) {
-#if KF_NT_STORES
                 __builtin_nontemporal_store(v4u{v[0], v[1], v[2], v[3]}, (v4u*)(row + g4));
-#else
-                *(v4u*)(row + g4) = v4u{v[0], v[1], v[2], v[3]};
-#endif
                 return;
             }
 #pragma unroll
@@ -859,20 +751,14 @@ bucket_kernel(CountArgs A, BucketArgs B) {
         Tbl tb = make_tbl(meta_at(0), re_next);
         Hv re_cur = re_next;
         re_next = meta_at(NBK > 1 ? 2 : 1);
-        Grp G0;
-#if KF_BK_DB
-        Grp G1;
-#endif
+        Grp G0, G1;
         issue(tb, G0);
-#if KF_BK_DB
         if constexpr (kPre2) issue(tb, G1);
-#endif
         uint64_t tp[4] = {0, 0, 0, 0};   // profile: records, barrier, flush, barrier
         uint64_t tcons = 0;              // profile: consume part of records
         for (uint32_t b = 0; b < NBK; ++b) {
             uint64_t t0 = B.prof ? __builtin_amdgcn_s_memtime() : 0;
             const uint32_t pm = ((b & L::hmask) << L::bits) * 0x10001u;   // both records of a word
-#if KF_BK_DB
             // two groups alternate: the bucket's next group is always in flight
             // while one is counted (issued unconditionally -- past the bucket's
             // end its lanes are inactive and read unit 0 -- so the compiler's
@@ -897,13 +783,6 @@ bucket_kernel(CountArgs A, BucketArgs B) {
                     if (G0.w0 >= tb.U) break;
                 }
             }
-#else
-            consume(G0, tb.U, pm);
-            while (tb.w0 < tb.U) {   // a bucket beyond one group: synchronous groups
-                issue(tb, G0);
-                consume(G0, tb.U, pm);
-            }
-#endif
             if (B.prof) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tcons += __builtin_amdgcn_s_memtime() - t0; }
             v2u ci[kFG];
             // issue order: bucket b+2's run ends, the flush's col_idx, bucket
@@ -915,9 +794,7 @@ bucket_kernel(CountArgs A, BucketArgs B) {
                 tb = make_tbl(re_cur, re_next);   // this bucket's run ends start the next
                 re_cur = re_next;
                 issue(tb, G0);
-#if KF_BK_DB
                 if constexpr (kPre2) issue(tb, G1);
-#endif
             }
             re_next = m;
             if (B.prof) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const uint64_t t = __builtin_amdgcn_s_memtime(); tp[0] += t - t0; t0 = t; }
@@ -969,7 +846,6 @@ void* bucket_ptr() { return (void*)&bucket_kernel<K>; }
 
 void* bucket_kernel_for(int k) {
     switch (k) {
-    case 9: return bucket_ptr<9>();
     case 10: return bucket_ptr<10>();
     case 11: return bucket_ptr<11>();
     case 12: return bucket_ptr<12>();
@@ -979,7 +855,6 @@ void* bucket_kernel_for(int k) {
 template <typename F>
 auto bucket_geom(int k, F f) {   // f(Bk<k>{}) for the compiled k
     switch (k) {
-    case 9: return f(Bk<9>{});
     case 10: return f(Bk<10>{});
     case 11: return f(Bk<11>{});
     default: return f(Bk<12>{});
@@ -987,12 +862,6 @@ auto bucket_geom(int k, F f) {   // f(Bk<k>{}) for the compiled k
 }
 uint32_t bucket_lds_for(int k) {
     return bucket_geom(k, [](auto b) { return decltype(b)::lds_bytes; });
-}
-int bucket_waves_for(int k) {
-    return bucket_geom(k, [](auto b) { return decltype(b)::waves; });
-}
-int bucket_bits_for(int k) {
-    return bucket_geom(k, [](auto b) { return decltype(b)::bits; });
 }
 
 // Per-device state: bucket tables per k and the scratch of the last launch
@@ -1010,26 +879,17 @@ struct DevState {
 DevState g_dev[64];
 std::mutex g_mu;
 
-uint32_t rc_std(uint32_t s, int k) {
-    uint32_t r = 0;
-    for (int i = 0; i < k; ++i) {
-        r = (r << 2) | (3u - (s & 3u));
-        s >>= 2;
-    }
-    return r;
-}
-
 int ensure_tables(DevState& d, int k) {
     if (d.col_idx[k]) return KF_OK;
-    const int bits = bucket_bits_for(k);
-    const uint32_t codes = 1u << bits;
+    constexpr int bits = kBkBits;
+    constexpr uint32_t codes = 1u << bits;
     const uint32_t ncode = 1u << (2 * k), nbk = ncode >> bits;
     std::vector<uint16_t> ci;
     std::vector<uint32_t> bc(nbk + 1, 0);
     ci.reserve(kf_num_bins(k));
     for (uint32_t s = 0; s < ncode; ++s) {
         if ((s & (codes - 1)) == 0) bc[s >> bits] = (uint32_t)ci.size();
-        if (s <= rc_std(s, k)) ci.push_back((uint16_t)(s & (codes - 1)));
+        if (s <= std_rc(s, k)) ci.push_back((uint16_t)(s & (codes - 1)));
     }
     bc[nbk] = (uint32_t)ci.size();
     if (ci.size() != kf_num_bins(k)) return kf_fail(KF_EINVAL, "bucket table: %zu canonical codes", ci.size());
@@ -1054,17 +914,15 @@ uint32_t rec_skew() {
 #endif
 }
 void scratch_layout(int cus, size_t& rec_b, size_t& meta_b, size_t& roff_b) {
-    rec_b = meta_b = roff_b = 0;
-    for (int kk = 9; kk <= KF_MAX_K; ++kk) {   // the bucket kernels: k >= 9
-        const size_t g = (size_t)cus * (16 / bucket_waves_for(kk)) * kBkSlots;
-        bucket_geom(kk, [&](auto b) {
-            using Lk = decltype(b);
-            rec_b = std::max(rec_b, g * (size_t)Lk::rec_cap * 2 + (size_t)128 * rec_skew());
-            meta_b = std::max(meta_b, g * ((size_t)Lk::nbk + 1) * Lk::rmax * 2);
-            roff_b = std::max(roff_b, g * (size_t)Lk::rmax * 4);
-            return 0;
-        });
-    }
+    // every term grows with the bucket count, so the largest k's geometry holds the others
+    using Lk = Bk<KF_MAX_K>;
+    static_assert(KF_MAX_K == 12 && Lk::nbk >= Bk<11>::nbk && Bk<11>::nbk >= Bk<10>::nbk &&
+                  Lk::rec_cap >= Bk<11>::rec_cap && Bk<11>::rec_cap >= Bk<10>::rec_cap &&
+                  Lk::rmax == Bk<11>::rmax && Lk::rmax == Bk<10>::rmax, "Bk<KF_MAX_K> dominates the compiled geometries");
+    const size_t g = (size_t)cus * kBkSlots;
+    rec_b = g * (size_t)Lk::rec_cap * 2 + (size_t)128 * rec_skew();
+    meta_b = g * ((size_t)Lk::nbk + 1) * Lk::rmax * 2;
+    roff_b = g * (size_t)Lk::rmax * 4;
 }
 
 }  // namespace
@@ -1076,8 +934,8 @@ int bucket_launch_info(int k, int* grid, int* block, int* lds) {
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         return kf_fail(KF_EHIP, "device query failed");
-    *grid = (cus > 0 ? cus : 1) * (16 / bucket_waves_for(k));
-    *block = bucket_waves_for(k) * kWave;
+    *grid = cus > 0 ? cus : 1;
+    *block = kBkWaves * kWave;
     *lds = (int)bucket_lds_for(k);
     return KF_OK;
 }
@@ -1100,30 +958,10 @@ int ensure_workspace(DevState& d, int dev, int k, int32_t n_genomes) {
     size_t rec_b = 0, meta_b = 0, roff_b = 0;
     scratch_layout(d.cus, rec_b, meta_b, roff_b);
     const size_t need = rec_b + meta_b + roff_b;
-#ifdef KF_PROFILE_BUILD
-    if (getenv("KF_BUCKET_TABLES_FIRST")) {
-        const int rc = ensure_tables(d, k);
-        if (rc) return rc;
-    }
-#endif
     rc0 = ensure_scratch(d, dev, need);
     if (rc0) return rc0;
-    // the tables after the scratch (KF_BUCKET_TABLES_FIRST=1, profiling builds:
-    // before it, the order of rounds 2-4)
-#ifdef KF_PROFILE_BUILD
-    const bool tables_first = getenv("KF_BUCKET_TABLES_FIRST") != nullptr;
-#else
-    const bool tables_first = false;
-#endif
-    if (!tables_first) {
-        const int rc = ensure_tables(d, k);
-        if (rc) return rc;
-    }
-#ifdef KF_PROFILE_BUILD
-    if (getenv("KF_BUCKET_DEBUG"))   // profiling builds: where the scratch and tables landed
-        fprintf(stderr, "[kf_bucket] scratch %p (%zu B) col_idx %p bcol %p\n", d.scratch, d.scratch_bytes,
-                (void*)d.col_idx[k], (void*)d.bcol[k]);
-#endif
+    rc0 = ensure_tables(d, k);   // the tables after the scratch
+    if (rc0) return rc0;
     if (d.pstart_n < (size_t)n_genomes + 1) {
         const size_t cap = std::max((size_t)n_genomes + 1, 2 * d.pstart_n);
         if (d.pstart && (hipDeviceSynchronize() != hipSuccess || hipFree(d.pstart) != hipSuccess))
@@ -1153,10 +991,6 @@ int ensure_scratch(DevState& d, int dev, size_t need) {
             return kf_fail(KF_EHIP, "hipFree of bucket scratch failed");
         d.scratch = nullptr;
         d.scratch_bytes = 0;
-#ifdef KF_PROFILE_BUILD
-        // profiling builds: KF_BUCKET_CONTIG=1 asks for physically contiguous scratch
-        if (!(getenv("KF_BUCKET_CONTIG") && hipExtMallocWithFlags(&d.scratch, need, hipDeviceMallocContiguous) == hipSuccess))
-#endif
         if (hipMalloc(&d.scratch, need) != hipSuccess)
             return kf_fail(KF_EHIP, "hipMalloc of %zu bytes of bucket scratch failed", need);
         d.scratch_bytes = need;
@@ -1183,8 +1017,8 @@ int bucket_launch(const CountArgs& A, int k, uint32_t flags, hipStream_t s) {
     int rc = ensure_workspace(d, dev, k, A.n_genomes);
     if (rc) return rc;
     const uint32_t lds = bucket_lds_for(k);
-    const int waves = bucket_waves_for(k);
-    const int grid = d.cus * (16 / waves);   // 16 waves per CU
+    constexpr int waves = kBkWaves;
+    const int grid = d.cus;   // one workgroup (16 waves) per CU
     size_t rec_b = 0, meta_b = 0, roff_b = 0;
     scratch_layout(d.cus, rec_b, meta_b, roff_b);
     if (d.done && hipStreamWaitEvent(s, d.done, 0) != hipSuccess)

@@ -1,9 +1,9 @@
-// kf_count.hip -- canonical k-mer counting kernels for k <= 8 on MI355X
+// kf_count.hip -- canonical k-mer counting kernels for k <= 9 on MI355X
 // (gfx950, CDNA4), the device half of kf_count_batch (include/kf2vec_gpu.h).
 //
 // Replaces the Jellyfish shell-out of kf2vec's get_frequencies (reference
 // kf2vec/main.py:309-328: `jellyfish count -C` + `jellyfish dump -c` + the
-// pandas merge onto the sorted vocabulary).  k >= 9 is kf_bucket.hip.
+// pandas merge onto the sorted vocabulary).  k >= 10 is kf_bucket.hip.
 //
 // Work decomposition:
 //   * the batch [goff[0], goff[n)) is cut into gridDim.x equal 16-byte-aligned
@@ -49,21 +49,8 @@ namespace kf {
 constexpr int kBlock = 1024;             // threads per workgroup
 // K1x: a genome piece's share per wave by the wave's age slot on its SIMD (the
 // SIMD issues oldest-first; slot 0 runs ~2.4x faster than slot 3), 8 bits each
-#ifndef KF_WAVE_WEIGHTS
-#define KF_WAVE_WEIGHTS (20u | 17u << 8 | 11u << 16 | 6u << 24)
-#endif
-constexpr uint32_t kWaveWeights = KF_WAVE_WEIGHTS;
+constexpr uint32_t kWaveWeights = 20u | 17u << 8 | 11u << 16 | 6u << 24;
 constexpr int kXRing = 2;    // K1x: 3 KiB iterations in the register ring
-
-__device__ __forceinline__ uint32_t lds_add_rtn(uint32_t a, uint32_t v) {
-    return __hip_atomic_fetch_add((lds_u32*)(uintptr_t)a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// Workgroup barrier ordering LDS only: waits for this wave's LDS operations, not
-// for its vector-memory ones (__syncthreads waits for vmcnt(0) too, i.e. for the
-// ring's prefetches and the flush's row stores; nothing here reads global
-// memory another wave of the workgroup wrote).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Byte span [lo, hi) of workgroup b of G over the batch (16-byte aligned).
 __device__ __forceinline__ void wg_span(const CountArgs& A, uint64_t& lo, uint64_t& hi) {
@@ -204,9 +191,6 @@ __device__ __forceinline__ uint32_t x_zmap(uint32_t x, uint32_t e, uint32_t c) {
 // formed and paired per 16-byte region: a lane holds 16 entries (15 with a
 // newline), the k-1 entries of context come from lane L-1's region by DPP, lane
 // 0 takes the previous region's lane 63.
-#ifndef KF_NT_STORES
-#define KF_NT_STORES 1   // non-temporal count-row stores (k=7 -1.4 %; v10_lib_ab_k*_nt_stores)
-#endif
 constexpr int kXNt = 2;   // buffer-load cache policy bit: non-temporal
 
 __device__ __forceinline__ XBlock xc_load(const uint8_t* bytes, uint64_t c0, uint32_t rel, uint32_t end_r, int lane) {
@@ -839,14 +823,10 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
             // the row writes last: their issue overlaps the zeroing, the barrier
             // and the next piece's setup
             if (whole && !any_drain) {
-#if KF_NT_STORES
+                // non-temporal (k=7 -1.4 %; profiles/r03/v10_lib_ab_k*_nt_stores.json)
                 typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
                 __builtin_nontemporal_store(v4u_t{cv[0], cv[1], cv[2], cv[3]}, (v4u_t*)(gc + 4 * tid));
                 __builtin_nontemporal_store(v4u_t{cv[4], cv[5], cv[6], cv[7]}, (v4u_t*)(gc + 4096 + 4 * tid));
-#else
-                *(uint4*)(gc + 4 * tid) = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-                *(uint4*)(gc + 4096 + 4 * tid) = make_uint4(cv[4], cv[5], cv[6], cv[7]);
-#endif
             } else {
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
@@ -1069,15 +1049,9 @@ extern "C" int kf_count_batch(const uint8_t* d_bytes, const uint64_t* d_goff, in
     if (((uintptr_t)d_bytes) & 15) return kf_fail(KF_EINVAL, "d_bytes must be 16-byte aligned");
     const uint64_t nb = kf_num_bins(k);
     hipStream_t s = (hipStream_t)stream;
-#ifdef KF_PROFILE_BUILD
-    // profiling builds: KF_K9_BUCKET=1 counts k = 9 with bucket_kernel<9> (the
-    // rounds 1-5 path), for A/B against K9b
-    const bool bucket = k >= 10 || (k == 9 && getenv("KF_K9_BUCKET") && atoi(getenv("KF_K9_BUCKET")));
-#else
     const bool bucket = k >= 10;
-#endif
     if (!(flags & KF_ACCUMULATE)) {
-        // k >= 9: the bucket kernels write every row themselves
+        // k >= 10: the bucket kernels write every row themselves
         if ((!bucket && hipMemsetAsync(d_counts, 0, (size_t)n_genomes * nb * sizeof(uint32_t), s) != hipSuccess) ||
             hipMemsetAsync(d_totals, 0, (size_t)n_genomes * sizeof(uint64_t), s) != hipSuccess)
             return kf_fail(KF_EHIP, "hipMemsetAsync failed");

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kf_scan.h"
+
 namespace kf {
 
 constexpr int kWave = 64;
@@ -163,29 +165,8 @@ __device__ __forceinline__ uint32_t run_mask(uint32_t E) {
     return R;
 }
 
-// Atomic add to the LDS word at byte address `a`.  The histogram is the whole
-// dynamic LDS allocation and the kernel declares no static LDS, so it starts at
-// LDS address 0 (checked once per kernel): a raw address-space-3 pointer avoids a
-// base add per k-mer.
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-__device__ __forceinline__ void lds_add(uint32_t a, uint32_t v) {
-    __hip_atomic_fetch_add((lds_u32*)(uintptr_t)a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
 __device__ __forceinline__ uint32_t wave_shr1(uint32_t old, uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x138, 0xF, 0xF, false);
-}
-
-// Inclusive prefix sum over the wave on the VALU (DPP row shifts and row
-// broadcasts; no LDS traffic, unlike __shfl_up's ds_bpermute).
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    return v;
 }
 
 // Exclusive scan of lane tails with a carry-in (slow path: some lane's block has
@@ -246,14 +227,13 @@ __device__ __forceinline__ void apply_masks(const CountArgs& A, uint64_t chunk, 
 // num_records, so an exact (unaligned) end would drop the genome's last bases.
 // Bytes in [ghi, align16(ghi)) are read but never counted (they lie past hi).
 // c = c0 + rel; end_r = align16(ghi) - c0 (32-bit: see process_range)
-#ifndef KF_CHUNK_CPOL
-#define KF_CHUNK_CPOL 2   // 1 KiB chunk stream: non-temporal (k=5 -1.3 %, k=9 -1.7 %, k=11 same; v10_lib_ab_*_chunk_nt)
-#endif
+// 1 KiB chunk stream: non-temporal (k=5 -1.3 %, k=9 -1.7 %, k=11 same; profiles/r03/v10_lib_ab_*_chunk_nt.json)
+constexpr int kChunkCpol = 2;
 __device__ __forceinline__ uint4 load_chunk(const uint8_t* bytes, uint64_t c0, uint32_t rel, uint32_t end_r,
                                             int lane) {
     const uint32_t rec = end_r > rel ? min(end_r - rel, (uint32_t)kChunk) : 0u;
     const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(bytes + c0 + rel), (short)0, (int)rec, 0x00020000);
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, 0, KF_CHUNK_CPOL);
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, 0, kChunkCpol);
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
@@ -367,17 +347,6 @@ struct Range {
         end_r = rel_of((ghi + 15) & ~(uint64_t)15);
         nch = (hi_r + kChunk - 1) / kChunk;
     }
-    template <int K>
-    __device__ __forceinline__ void begin(const CountArgs& A, uint64_t glo_, uint64_t ghi_, uint64_t lo_,
-                                          uint64_t hi_, int lane) {
-        init(glo_, ghi_, lo_, hi_);
-        warm<K>(A, lane);
-    }
-    // Lane block of the chunk before c0 (the first warm-up step), so its load can
-    // be issued early; pass it to warm_from.
-    __device__ __forceinline__ uint4 ctx_load(const uint8_t* bytes, int lane) const {
-        return c0 > glo ? chunk_tail_load(bytes, (int64_t)c0 - kChunk, glo, lane) : make_uint4(0u, 0u, 0u, 0u);
-    }
     // Context and first interval (after init).
     template <int K>
     __device__ __forceinline__ void warm(const CountArgs& A, int lane) {
@@ -418,21 +387,6 @@ struct Range {
         ivs_r = iv < A.n_excl ? rel_of(s_iv) : 0xFFFFFFFFu;
         ive_r = iv < A.n_excl ? rel_of(e_iv) : 0xFFFFFFFFu;
         ivs_a = s_iv, ive_a = e_iv;
-    }
-    // As warm, with the first chunk before c0 already loaded (ctx_load).
-    template <int K>
-    __device__ __forceinline__ void warm_from(const CountArgs& A, const uint4 dctx, int lane) {
-        carry = tail_pack(0, 0, 0);
-        int64_t p = (int64_t)c0;
-        if (p > (int64_t)glo) {
-            p -= kChunk;
-            carry = chunk_tail_data<K>(dctx, A.bytes, A.excl, A.n_excl, p, glo, lane);
-        }
-        for (; p > (int64_t)glo && !tail_complete<K>(carry);) {   // rare: a short chunk of context
-            p -= kChunk;
-            carry = tail_combine<K>(chunk_tail<K>(A.bytes, A.excl, A.n_excl, p, glo, lane), carry);
-        }
-        find_interval(A, lane);
     }
     __device__ __forceinline__ void find_interval(const CountArgs& A, int lane) {
         // first excluded interval ending after c0; its bounds live in registers so

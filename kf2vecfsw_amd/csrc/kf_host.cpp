@@ -43,7 +43,9 @@ inline uint64_t kf_to_std(uint64_t x, int k) {
     const uint64_t lo = 0x5555555555555555ull & ((k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1));
     return x ^ ((x >> 1) & lo);
 }
-inline uint64_t std_rc(uint64_t x, int k) {
+}  // namespace
+
+uint64_t std_rc(uint64_t x, int k) {
     uint64_t r = 0;
     for (int i = 0; i < k; ++i) {
         r = (r << 2) | (3u - (x & 3u));
@@ -51,7 +53,6 @@ inline uint64_t std_rc(uint64_t x, int k) {
     }
     return r;
 }
-}  // namespace
 
 int kf_fail(int code, const char* fmt, ...) {
     char buf[512];

@@ -8,3 +8,5 @@
 // Records the thread-local error message and returns `code`.
 int kf_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// Reverse complement of a k-mer in lexicographic code (A0 C1 G2 T3; kf_host.cpp).
+uint64_t std_rc(uint64_t x, int k);

@@ -47,6 +47,7 @@
 #include <cstdio>
 
 #include "kf_internal.h"
+#include "kf_scan.h"
 
 namespace kf {
 namespace {
@@ -71,71 +72,36 @@ constexpr int kBWaves = kBBlock / 64;          // 8
 constexpr int kBD = 10;
 constexpr uint32_t kNB = 1u << kBD;
 __host__ __device__ constexpr int sp_dbits(int k) { return 2 * k < kBD ? 2 * k : kBD; }
-// Phase C: chunks of at most 32 keys per thread (16,384 at 512 threads: 128 KiB
-// of LDS for u64 keys), up to 256 VGPRs per thread (1024 threads spilled at 128).
-// tools/ A/B builds: KF_SP_CBLOCK = 256, 8,192-key chunks, two workgroups per CU;
-// KF_SP_CBLOCK = 768 with KF_SP_CPER = 16 keys per thread, 12,288-key chunks
-// and 12 waves per CU.
-#ifndef KF_SP_CBLOCK
-#define KF_SP_CBLOCK 512
-#endif
-#ifndef KF_SP_CPER
-#define KF_SP_CPER 32
-#endif
-constexpr int kCBlock = KF_SP_CBLOCK;
+// Phase C: 512-thread workgroups, chunks of at most 32 keys per thread (16,384:
+// 128 KiB of LDS for u64 keys), up to 256 VGPRs per thread (1024 threads spilled
+// at 128).
+constexpr int kCBlock = 512;
 constexpr int kCWaves = kCBlock / 64;
-constexpr uint32_t kCCap = (uint32_t)KF_SP_CPER * (uint32_t)kCBlock;
-constexpr int kCPerCU = kCBlock >= 512 ? 1 : 512 / kCBlock;   // resident chunk workgroups per CU
+constexpr int kCPer8 = 32;   // keys per thread, u64 keys
 // u32 keys (k <= 16): 24 keys per thread, 12,288-key chunks, so a chunk
-// workgroup needs <= 80 KiB of LDS and two share a CU (4 waves per SIMD; the
-// 128-VGPR budget spills ~140 B per lane): k = 13 5.67-5.68 ms against
-// 5.84 with one 16,384-key workgroup per CU, k = 16 5.86-5.87 against 5.95
-// (processes alternated, profiles/r06/v33_sparse_u32_2wg_ab.jsonl)
-#ifndef KF_SP_CPER4
-#define KF_SP_CPER4 24
-#endif
+// workgroup needs <= 80 KiB of LDS and two share a CU (4 waves per SIMD): k = 13
+// 5.67 ms against 5.84 with one 16,384-key workgroup per CU
+// (profiles/r06/v33_sparse_u32_2wg_ab.jsonl)
+constexpr int kCPer4 = 24;
 constexpr uint32_t kNoOvf = 0xFFFFFFFFu;
-// 8-bit MSD passes over the top bits of a chunk's keys before the run fix-up
-// (tools/ A/B builds: KF_SP_MSD=3 sorts 24 bits, leaving almost no runs).
-#ifndef KF_SP_MSD
-#define KF_SP_MSD 2
-#endif
-// Digit width of the chunk sort's passes (KF_SP_DIGIT = 8 or 10): 10-bit MSD
-// passes sort the top 20 bits, so a 16,384-key chunk over 2^20 values leaves
-// runs of equal top bits for ~1.6 % of its keys instead of ~22 %, and a chunk
-// whose keys span R = 2k - D + ceil(log2 buckets) <= 20 bits is sorted whole in
-// the two passes (D = 10 bucket bits: k <= 15 for a one-bucket chunk, k <= 14
-// for the usual two to four buckets per chunk).  64 x 5 Mbp (profiles/r05/v19_*):
-// k = 31 7.69 -> 7.23 ms, k = 13 6.37 -> 5.97 (fix-up 0.69e9 -> 0.38e9 cycles,
-// the passes unchanged; 16 KiB of counters per workgroup instead of 4).
-// Phase A loads a workgroup's next tile's bytes while it makes this tile's keys
-// (KF_SP_PREFETCH_A=0: when the tile starts).
-#ifndef KF_SP_PREFETCH_A
-#define KF_SP_PREFETCH_A 1
-#endif
-// Unroll of the chunk kernel's mask sweep and run-length stores (tools/ A/B).
-#ifndef KF_SP_UNROLL_SWEEP
-#define KF_SP_UNROLL_SWEEP 4
-#endif
-#ifndef KF_SP_UNROLL_STORES
-#define KF_SP_UNROLL_STORES 4
-#endif
-#ifndef KF_SP_DIGIT
-#define KF_SP_DIGIT 10
-#endif
-constexpr int kDB = KF_SP_DIGIT;
+// Chunk sort: kMsdPasses MSD passes of kDB bits over the top bits of a chunk's
+// keys before the run fix-up.  Two 10-bit passes sort the top 20 bits, so a
+// 16,384-key chunk over 2^20 values leaves runs of equal top bits for ~1.6 % of
+// its keys (8-bit passes: ~22 %): k = 31 7.69 -> 7.23 ms (profiles/r05/v19_*).
+constexpr int kMsdPasses = 2;
+constexpr int kDB = 10;
 constexpr uint32_t kND = 1u << kDB;          // digits
 constexpr uint32_t kNWW = kND / 2;           // packed u16 counter words per wave
 template <typename KeyT>
 struct ChunkOf {
-    static constexpr int per = sizeof(KeyT) == 4 ? KF_SP_CPER4 : KF_SP_CPER;   // keys per thread
+    static constexpr int per = sizeof(KeyT) == 4 ? kCPer4 : kCPer8;            // keys per thread
     static constexpr uint32_t cap = (uint32_t)per * (uint32_t)kCBlock;         // keys
     static constexpr uint32_t wave_span = cap / kCWaves;
     // LDS: the key stage, the digit counters, the head-mask prefixes, wsum, cid
     static constexpr uint32_t lds = cap * (uint32_t)sizeof(KeyT) + kCWaves * kNWW * 4 + (cap / 32) * 4 +
                                     kCWaves * 4 + 16;
-    static constexpr int per_cu = kCPerCU == 1 && 2 * lds <= 160u * 1024u ? 2 : kCPerCU;
-    static constexpr int waves_per_eu = (kCWaves * per_cu + 3) / 4;
+    static constexpr int per_cu = 2 * lds <= 160u * 1024u ? 2 : 1;   // resident chunk workgroups per CU
+    static constexpr int waves_per_eu = kCWaves * per_cu / 4;
 };
 struct Chunk {          // one LDS sort unit: buckets [blo, blo + nb) of one genome
     uint32_t start;     // first slot in the bucketed keys
@@ -185,31 +151,14 @@ __device__ __forceinline__ bool tile_span(const uint64_t* goff, const uint32_t* 
     return true;
 }
 
-// Barrier for LDS traffic only: outstanding global loads and stores stay in
-// flight across it (__syncthreads() is a workgroup fence too, which waits for
-// every outstanding global access of the wave first).
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Inclusive prefix sum over a whole (fully active) wave on the VALU: DPP row
-// shifts and row broadcasts instead of __shfl_up's six ds_bpermute round trips.
-__device__ __forceinline__ uint32_t wave_incl_dpp(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    return v;
-}
-
 // Exclusive prefix of one value per thread over an NW-wave workgroup; *total
 // (optional) gets the sum.  Contains two barriers (LDS-only ones if LDSB).
 template <int NW, bool LDSB = false>
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total = nullptr) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t inc = wave_incl_dpp(v);
+    const uint32_t inc = wave_incl_scan(v);
     if (lane == 63) wsum[w] = inc;
-    if (LDSB) lds_sync();
+    if (LDSB) lds_barrier();
     else __syncthreads();
     uint32_t before = 0, all = 0;
 #pragma unroll
@@ -219,7 +168,7 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, 
         all += s;
     }
     if (total) *total = all;
-    if (LDSB) lds_sync();
+    if (LDSB) lds_barrier();
     else __syncthreads();
     return before + inc - v;
 }
@@ -529,12 +478,10 @@ __global__ void __launch_bounds__(kSBlock) sp_ghist_kernel(const KeyT* __restric
 // units ordered by (index inside the segment, segment), so the units running at
 // once spread over the segments' independent look-back chains instead of
 // queueing on one chain.  Inside a segment the order is kept (what the
-// look-back's progress needs).  O(n) per unit: used up to KF_SPARSE_ORDER_MAXN
+// look-back's progress needs).  O(n) per unit: used up to kSparseOrderMaxN
 // segments (identity above).  ufirst: prefix of units per segment, the total at
 // [n], the unit -> segment map from [n + 2].
-#ifndef KF_SPARSE_ORDER_MAXN
-#define KF_SPARSE_ORDER_MAXN 4096
-#endif
+constexpr int kSparseOrderMaxN = 4096;
 __global__ void __launch_bounds__(kSBlock) sp_order_kernel(const uint32_t* ufirst, int n, uint32_t* order) {
     const uint32_t t = blockIdx.x * kSBlock + threadIdx.x;
     if (t >= ufirst[n]) return;
@@ -653,11 +600,9 @@ __global__ void __launch_bounds__(kBBlock) sp2_count_kernel(const uint8_t* __res
     EmitIn in = emit_load(bytes, ts, nbytes);
     for (uint32_t t = t0 + blockIdx.y; t < t1; t += gridDim.y) {
         // this workgroup's next tile's bytes go out before this tile's keys are made
-        // (KF_SP_PREFETCH_A=0, tools/ builds: loaded when the tile starts)
         TileSpan tn = ts;
         EmitIn inn = in;
-        if (!KF_SP_PREFETCH_A) in = emit_load(bytes, ts, nbytes);
-        if (KF_SP_PREFETCH_A && t + gridDim.y < t1) {
+        if (t + gridDim.y < t1) {
             tile_span(goff, tfirst, n, t + gridDim.y, tn, kTB);
             inn = emit_load(bytes, tn, nbytes);
         }
@@ -679,12 +624,8 @@ __global__ void __launch_bounds__(kBBlock) sp2_count_kernel(const uint8_t* __res
             for (int j = 0; j < kEB; ++j)
                 if (out[j] != sent) atomicAdd(&h[(uint32_t)(out[j] >> bshift)], 1u);
         }
-        if (KF_SP_PREFETCH_A) {
-            ts = tn;
-            in = inn;
-        } else if (t + gridDim.y < t1) {
-            tile_span(goff, tfirst, n, t + gridDim.y, ts, kTB);
-        }
+        ts = tn;
+        in = inn;
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < kNB; i += kBBlock)
@@ -769,7 +710,7 @@ __global__ void __launch_bounds__(kBBlock) sp2_scatter_kernel(const uint8_t* __r
         uint32_t xt = 0;
         if (tid == 0 && hn) xt = atomicAdd(ticket, 1u);   // the tile after tn (published at the end)
         for (int i = tid; i < kBWaves * (int)kNB / 2; i += kBBlock) (&wc[0][0])[i] = 0;
-        lds_sync();
+        lds_barrier();
         tick(0);
         uint32_t rk[kEB];
 #pragma unroll
@@ -777,7 +718,7 @@ __global__ void __launch_bounds__(kBBlock) sp2_scatter_kernel(const uint8_t* __r
             const uint32_t b = (uint32_t)(key[j] >> bshift), sh = (b & 1u) << 4;
             rk[j] = key[j] != sent ? (atomicAdd(&wc[w][b >> 1], 1u << sh) >> sh) & 0xFFFFu : 0u;
         }
-        lds_sync();
+        lds_barrier();
         tick(1);
         {
             // thread tid: buckets 2 tid, 2 tid + 1 (word tid of every wave's row)
@@ -802,7 +743,7 @@ __global__ void __launch_bounds__(kBBlock) sp2_scatter_kernel(const uint8_t* __r
             gdst[b1] = b1 < nbe ? gbase[(uint64_t)ts.g * kNB + b1] + bf1 - (ex + t0c) : 0u;
             if (tid == 0) nvalid = all;
         }
-        lds_sync();
+        lds_barrier();
         tick(2);
 #pragma unroll
         for (int j = 0; j < kEB; ++j) {
@@ -811,7 +752,7 @@ __global__ void __launch_bounds__(kBBlock) sp2_scatter_kernel(const uint8_t* __r
                 stage[lbase[b] + ((wc[w][b >> 1] >> sh) & 0xFFFFu) + rk[j]] = key[j];
             }
         }
-        lds_sync();
+        lds_barrier();
         tick(3);
         const uint32_t nv = nvalid;
         for (uint32_t i = tid; i < nv; i += kBBlock) {
@@ -819,7 +760,7 @@ __global__ void __launch_bounds__(kBBlock) sp2_scatter_kernel(const uint8_t* __r
             out[gdst[(uint32_t)(x >> bshift)] + i] = x;
         }
         if (tid == 0 && hn) tix = take(xt);
-        lds_sync();   // stage, gdst, tix are reused by the next tile
+        lds_barrier();   // stage, gdst, tix are reused by the next tile
         tick(4);
         t = tn;
         ts = tsn;
@@ -952,7 +893,7 @@ __device__ __forceinline__ uint32_t ceil_log2(uint32_t x) { return x <= 1 ? 0u :
 // ---- C2. chunk sort + run-length encoding (persistent, one 512-thread
 // workgroup per CU).  A chunk's keys (minus its first bucket's base: R = B +
 // ceil(log2 nb) bits) are loaded striped, 32 per thread, and sorted in LDS by
-// stable 10-bit passes (KF_SP_DIGIT): per pass a returning packed-u16 LDS add per
+// stable 10-bit passes (kDB): per pass a returning packed-u16 LDS add per
 // key into its wave's digit counter (stable: an LDS unit serves one
 // instruction's lanes in lane order, and keys are striped so lane, then
 // iteration, then wave is slot order), every thread turns two digits' 8 counters
@@ -1051,13 +992,13 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
             const uint32_t R = (uint32_t)bshift + ceil_log2(ch.nb);
             auto pass = [&](int sh8, bool reload) __attribute__((always_inline)) {
                 for (int i = tid; i < kCWaves * (int)kNWW; i += kCBlock) (&wc[0][0])[i] = 0;
-                lds_sync();
+                lds_barrier();
 #pragma unroll
                 for (int it = 0; it < PER; ++it) {
                     const uint32_t d = (uint32_t)(y[it] >> sh8) & (kND - 1u), sh = (d & 1u) << 4;
                     rk[it] = (atomicAdd(&wc[w][d >> 1], 1u << sh) >> sh) & 0xFFFFu;
                 }
-                lds_sync();
+                lds_barrier();
                 {
                     // thread t: digits 2t, 2t + 1 (word t of every wave's row), all waves at
                     // once.  Every counter becomes its keys' first slot: the digit's start
@@ -1081,13 +1022,13 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
                         }
                     }
                 }
-                lds_sync();
+                lds_barrier();
 #pragma unroll
                 for (int it = 0; it < PER; ++it) {
                     const uint32_t d = (uint32_t)(y[it] >> sh8) & (kND - 1u), sh = (d & 1u) << 4;
                     stage[((wc[w][d >> 1] >> sh) & 0xFFFFu) + rk[it]] = y[it];
                 }
-                lds_sync();
+                lds_barrier();
                 if (reload) {
 #pragma unroll
                     for (int it = 0; it < PER; ++it) y[it] = srow[it * 64];
@@ -1095,13 +1036,13 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
             };
             constexpr uint32_t kRun = 32;
             for (int round = 0; round < 2; ++round) {
-                const bool msd = round == 0 && R > (uint32_t)(kDB * KF_SP_MSD);
-                const int lo = msd ? (int)R - kDB * KF_SP_MSD : 0;
-                const int np = msd ? KF_SP_MSD : (int)((R + kDB - 1) / kDB);
+                const bool msd = round == 0 && R > (uint32_t)(kDB * kMsdPasses);
+                const int lo = msd ? (int)R - kDB * kMsdPasses : 0;
+                const int np = msd ? kMsdPasses : (int)((R + kDB - 1) / kDB);
                 if (np == 0) {   // one key value: already sorted
 #pragma unroll
                     for (int it = 0; it < PER; ++it) srow[it * 64] = y[it];
-                    lds_sync();
+                    lds_barrier();
                 }
                 for (int p = 0; p < np; ++p) {
                     pass(lo + kDB * p, p + 1 < np);
@@ -1111,7 +1052,7 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
                 // (the keys differ); the order check on the sorted bits (every key is in
                 // order when lo = 0).  Consecutive lanes read consecutive slots.
                 bool disorder = false;
-#pragma unroll KF_SP_UNROLL_SWEEP
+#pragma unroll 4
                 for (int it = 0; it < PER; ++it) {
                     const uint32_t i = li0 + (uint32_t)it * 64;
                     const KeyT v = srow[it * 64], pv = i ? stage[i - 1] : (KeyT)0;
@@ -1127,7 +1068,7 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
                     }
                 }
                 if (__ballot(disorder) && lane == 0) atomicOr(flags, 2u | 16u);   // the sort's self-check
-                lds_sync();
+                lds_barrier();
                 if (!msd) break;
                 // runs of two or more keys start where a start bit is followed by a clear
                 // one: rare; the thread owning the start's word sorts the run and
@@ -1172,7 +1113,7 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
                 if (!again) break;
 #pragma unroll
                 for (int it = 0; it < PER; ++it) y[it] = srow[it * 64];
-                lds_sync();
+                lds_barrier();
             }
         }
         // ---------------------------------------------------- next chunk: its keys into y now
@@ -1208,10 +1149,10 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
                 before_s = bf;
                 if (last) unq[g] = (uint64_t)bf + nu;
             }
-            lds_sync();
+            lds_barrier();
             tick(4);
             const uint64_t o0 = goff[g] + before_s;
-#pragma unroll KF_SP_UNROLL_STORES
+#pragma unroll 4
             for (int it = 0; it < PER; ++it) {
                 const uint32_t i = li0 + (uint32_t)it * 64;
                 if (i >= nk) continue;
@@ -1230,7 +1171,7 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
                 ocounts[o0 + j] = min(nx, nk) - i;
             }
             if (tid == 0 && cn < total) cid = take(xt);
-            lds_sync();   // stage, masks, cid are reused by the next chunk
+            lds_barrier();   // stage, masks, cid are reused by the next chunk
             tick(5);
         } else if (have) {
             // ------------------------------------------------ big bucket (sorted in the overflow area)
@@ -1286,9 +1227,9 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
             __syncthreads();
         } else {
             // no chunk yet (first iteration): every thread has read cid by now
-            lds_sync();
+            lds_barrier();
             if (tid == 0 && cn < total) cid = take(xt);
-            lds_sync();
+            lds_barrier();
         }
         if (cn >= total) {
             if (prof && tid == 0)
@@ -1439,7 +1380,7 @@ int sp_run(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n, uint64_t b
 #endif
     // B: scatter by bucket
     uint32_t* border = nullptr;
-    if (n > 1 && n <= KF_SPARSE_ORDER_MAXN) {
+    if (n > 1 && n <= kSparseOrderMaxN) {
         border = at32(L.border);
         hipLaunchKernelGGL(sp_order_kernel, dim3(L.tiles / kSBlock + 1), dim3(kSBlock), 0, s, tfirst, n, border);
     }
@@ -1480,7 +1421,7 @@ int sp_run(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n, uint64_t b
         hipLaunchKernelGGL(sp_ghist_kernel<KeyT>, dim3((uint32_t)min(S, 4 * cus)), dim3(kSBlock), 0, s, src, seg_off,
                            otfirst, S, passes, bits, B, gall);
         uint32_t* oorder = nullptr;
-        if (S > 1 && S <= KF_SPARSE_ORDER_MAXN) {
+        if (S > 1 && S <= kSparseOrderMaxN) {
             oorder = at32(L.oorder);
             hipLaunchKernelGGL(sp_order_kernel, dim3(L.otiles / kSBlock + 1), dim3(kSBlock), 0, s, otfirst, S, oorder);
         }
@@ -1502,7 +1443,7 @@ int sp_run(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n, uint64_t b
     }
     // C2: chunks
     uint32_t* corder = nullptr;
-    if (n > 1 && n <= KF_SPARSE_ORDER_MAXN) {
+    if (n > 1 && n <= kSparseOrderMaxN) {
         corder = at32(L.corder);
         hipLaunchKernelGGL(sp_order_kernel, dim3(L.cmax / kSBlock + 1), dim3(kSBlock), 0, s, at32(L.cfirst), n, corder);
     }

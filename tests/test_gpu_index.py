@@ -96,3 +96,50 @@ def test_device_index_table_regrows(torch_dev):
     nl = hb_host.data.numpy()[:n] == 10
     got = excluded_mask(db.excl[: 2 * db.n_excl].cpu().numpy(), n)
     assert np.array_equal(got & ~nl, excluded_mask(hb_host.excl, n) & ~nl)
+
+
+def test_device_index_scan_carry_past_1024_blocks(torch_dev):
+    """One batch of 2,050 index blocks of 4 KiB (2 x 1024 x 4096 + 4096 + 5 bytes),
+    so the one-workgroup block scan runs three 1,024-block iterations and the pairs
+    of blocks 1024.. and 2048.. depend on its carry.  Two genomes; header lines
+    start in blocks 0, 1023, 1024, 2047, 2048 and 2049: one '>' is the last byte
+    of block 1023 (its line runs to the genome end, no newline) and the second
+    genome's '>' is the first byte of block 1024 with no newline before it."""
+    import torch
+    from kf2vecfsw_amd import counter as C
+    from kf2vecfsw_amd import _native as N
+    B = 4096
+    n = 2 * 1024 * B + B + 5
+    g1 = 1024 * B                                   # start of the second genome
+    rng = np.random.default_rng(47)
+    d = gen.BASES[rng.integers(0, 4, size=n)].copy()
+    d[60::61] = 10
+    exp = []
+
+    def header(at, text, newline=True):             # a header line at `at` (a line start)
+        if at not in (0, g1):
+            d[at - 1] = 10
+        d[at: at + len(text)] = np.frombuffer(text, np.uint8)
+        if newline:
+            d[at + len(text)] = 10
+        exp.extend([at, at + len(text)])
+
+    header(0, b">g0 first")                          # block 0
+    header(g1 - 1, b">", newline=False)              # last byte of block 1023, ends with its genome
+    header(g1, b">g1 no newline before")             # first byte of block 1024
+    header(2047 * B + 100, b">in 2047")
+    header(2048 * B + 7, b">in 2048 > x")
+    header(n - 4, b">end", newline=False)            # block 2049 (5 bytes), runs to the batch end
+    assert [e // B for e in exp[0::2]] == [0, 1023, 1024, 2047, 2048, 2049]
+    assert d[g1 - 2] == 10 and d[g1 - 1] == ord(">") and d[g1] == ord(">")
+    off = np.array([0, g1, n], dtype=np.uint64)
+    data = torch.full((n + 16,), 10, dtype=torch.uint8)
+    data.numpy()[:n] = d
+    db = C.to_device(C.HostBatch(data, off, None, ["a", "b"]), torch_dev)
+    torch.cuda.synchronize()
+    pairs = db.excl[: 2 * db.n_excl].cpu().numpy()
+    assert pairs.tolist() == exp, (pairs.tolist(), exp)
+    host = np.concatenate([C.index_records(d[int(off[i]): int(off[i + 1])], N.KF_FMT_FASTA, int(off[i]))[0]
+                           for i in range(2)])
+    nl = d == 10
+    assert np.array_equal(excluded_mask(pairs, n) & ~nl, excluded_mask(host, n) & ~nl)

@@ -822,6 +822,42 @@ def test_chunk_compact_matches_oracle(torch_dev, oracle):
     pipe.close()
 
 
+def test_chunk_compact_scan_carry_past_1024_blocks(torch_dev, oracle):
+    """One record of 2,050 compaction blocks of 4 KiB (2 x 1024 x 4096 + 4096 + 5
+    bytes, 60-column lines), so the one-workgroup block scan runs three
+    1,024-block iterations and the output positions of blocks 1024.. and 2048..
+    depend on its carry.  N runs straddle the 1023/1024 and 2047/2048 block edges
+    and a gap letter is the first byte of block 2048 (it splits that run in two)."""
+    from kf2vecfsw_amd import chunks as CH
+    from kf2vecfsw_amd import counter as C
+    from kf2vecfsw_amd import _native as N
+    B = 4096
+    n = 2 * 1024 * B + B + 5
+    rng = np.random.default_rng(4141)
+    hdr = b">ctg0 x\n"
+    d = gen.BASES[rng.integers(0, 4, size=n)].copy()
+    d[: len(hdr)] = np.frombuffer(hdr, np.uint8)
+    d[len(hdr) + 60:: 61] = 10                       # 60-column lines
+    seq = d != 10
+    for edge in (1024 * B, 2048 * B):
+        run = np.arange(edge - 70, edge + 70)        # spans a line break as well
+        d[run[seq[run]]] = np.frombuffer(b"Nn|N", np.uint8)[run[seq[run]] % 4]
+    assert seq[2048 * B]
+    d[2048 * B] = ord("-")
+    data = d.tobytes()
+    hb = C.pack_genomes([data], ["s0"], fmt=N.KF_FMT_FASTA)
+    assert int(hb.off[-1]) == n + 11 and (n + 11 + B - 1) // B == 2050   # (padded to 16 bytes)
+    genomes = [CH.Genome("s0.fna", "s0")]
+    pipe = CH.ChunkPipeline(counter(7, torch_dev), torch_dev, 16, 2)
+    got = pipe.prepare(hb, genomes).cpu().numpy()
+    exp = oracle.chunk_windows(data, "s0")
+    assert len(exp) > 800 and genomes[0].names == [nm for nm, _ in exp]
+    for st, (_, w) in zip(genomes[0].starts, exp):
+        assert got[int(st): int(st) + 10000].tobytes() == w
+    assert genomes[0].excluded is None
+    pipe.close()
+
+
 def test_cli_get_chunks_multicontig_vs_oracle(torch_dev, oracle, tmp_path):
     """get_chunks CLI on several multi-contig genomes (one device batch, then a
     batch smaller than a genome's windows): every row == the oracle's window

@@ -124,7 +124,7 @@ def test_sparse_ragged_tile_counts_interleaved_order(torch_dev, oracle):
 
 
 def test_sparse_more_genomes_than_the_order_table(torch_dev, oracle):
-    """5,000 genomes in one batch (past KF_SPARSE_ORDER_MAXN = 4,096: tiles run
+    """5,000 genomes in one batch (past kSparseOrderMaxN = 4,096: tiles run
     in plain order)."""
     rng = np.random.default_rng(78)
     blobs = [gen.random_seq(rng, int(L)).tobytes()[: int(L)] for L in rng.integers(0, 400, 5000)]

@@ -28,6 +28,30 @@ def test_exports_every_header_symbol(native):
     assert native.kf_abi_version() == 1
 
 
+def test_csrc_has_no_build_knobs():
+    """Every preprocessor conditional in csrc/ is an include guard,
+    KF_PROFILE_BUILD or KF_BUILD_ID: a measured and settled choice is a constexpr
+    next to its use, not a macro that leaves the other arm in the source
+    ("settled build knobs")."""
+    csrc = os.path.join(ROOT, "kf2vecfsw_amd", "csrc")
+    allowed = {"KF_PROFILE_BUILD", "KF_BUILD_ID"}
+    bad, seen = [], 0
+    for name in sorted(os.listdir(csrc)):
+        lines = open(os.path.join(csrc, name)).read().splitlines()
+        for i, ln in enumerate(lines):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", ln)
+            if not m:
+                continue
+            seen += 1
+            cond = m.group(2).split("//")[0].strip()
+            guard = m.group(1) == "ifndef" and i + 1 < len(lines) and \
+                re.fullmatch(r"\s*#\s*define\s+%s\s*" % re.escape(cond), lines[i + 1]) and cond.endswith("_H")
+            if not guard and re.sub(r"^defined\s*\(?\s*(\w+)\s*\)?$", r"\1", cond) not in allowed:
+                bad.append("%s:%d: %s" % (name, i + 1, ln.strip()))
+    assert seen >= 3, "the scan found no conditionals at all"
+    assert not bad, "\n".join(bad)
+
+
 def test_tables_match_oracle(native, oracle):
     from kf2vecfsw_amd import counter as C
     for k in range(2, 12):

@@ -14,7 +14,7 @@
 #   alt=K:REPS:ROUNDS:V1,V2  processes alternated (one per library and repetition,
 #                 tools/r04_run.py at k=K): kf2vecfsw_amd/libkf2vec_gpu_<V>.so, "product"
 #                 = the product library; ENV:NAME=VAL entries instead run the product
-#                 with that variable (e.g. ENV:KF_K9_BUCKET=1 with the ablation build)
+#                 with that variable (e.g. ENV:KF_BUCKET_PROFILE=1 with the ablation build)
 #                 -> alt_N.jsonl (the round-5 k11 / k9 / coop / db / barrier A/Bs)
 #   libab=K:V1,V2 in-process A/B of library variants (tools/lib_ab.py) -> libab_N.json
 #   pmc=K:LIB:G1;G2  rocprofv3 --pmc passes, one counter group per pass (';' between
