@@ -107,11 +107,60 @@ int kf_read_files(const char* const* paths, int32_t n, const uint64_t* sizes, co
  * count kernels treat alike).  *d_n_pairs (device) receives the number of
  * header lines; only the first cap_pairs are written, so a caller reads it back
  * and runs again with a larger table if it was exceeded.  batch_bytes = goff[n];
- * d_scratch >= ceil(batch_bytes / 4096) + 1 words.  FASTA only (FASTQ needs
- * kf_index_records' per-file state).  Asynchronous on `stream`. */
+ * d_scratch >= ceil(batch_bytes / 4096) + 1 words.  FASTA only (a FASTQ batch
+ * goes to kf_index_fastq).  Asynchronous on `stream`. */
 int kf_index_fasta(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n_genomes,
                    uint64_t batch_bytes, uint64_t* d_excl, uint64_t cap_pairs,
                    uint64_t* d_n_pairs, uint32_t* d_scratch, uint64_t scratch_words, void* stream);
+
+/* The FASTQ record index of a batch resident in HBM: every genome of a batch
+ * laid out as for kf_count_batch (d_bytes 16-byte aligned and readable up to
+ * batch_bytes = goff[n] rounded up to 16) is read as FASTQ in the regular
+ * four-line form.  With j the 0-based number of a line inside its genome (lines
+ * end at '\n' only, a genome's first line starts at goff[g]) and L its length
+ * without the '\n' ('\r' counts), a genome is REGULAR if for every line up to
+ * its last non-empty one
+ *   j % 4 == 0: L > 0 and the line starts with '@';
+ *   j % 4 == 1: the line is empty or does not start with '+';
+ *   j % 4 == 2: L > 0 and the line starts with '+';
+ *   j % 4 == 3: L >= L(line j - 2), and the line is empty if line j - 2 is.
+ * Trailing empty lines (the '\n' padding included), a genome that stops in the
+ * middle of a record and one without a final '\n' stay regular.  For a regular
+ * genome the excluded bytes of kf_index_records(KF_FMT_FASTQ) are the bytes of
+ * every line with j % 4 != 1, and this call writes them as sorted, disjoint,
+ * non-empty [start, end) pairs d_excl[2i], d_excl[2i+1] (absolute positions,
+ * the form kf_count_batch takes): one pair for the genome's first header line,
+ * then one per record that has a '+' line, from the start of that line to the
+ * end of the next record's header line (or of the genome's last non-empty
+ * line) -- records + 1 pairs for a genome of whole records, none for a genome
+ * of '\n' only.  No pair crosses goff[g + 1].
+ *   d_n[0] (device) : the number of pairs; only the first cap_pairs are written
+ *   d_n[1] (device) : the number of '\n' in the batch.  The index works from a
+ *                     table of their positions that holds cap_lines entries; if
+ *                     d_n[1] > cap_lines nothing else was computed (d_n[0] = 0)
+ *   d_status[g]     : 0 = regular; 1 = not regular; 2 = goff[g] > goff[g + 1] or
+ *                     goff[g + 1] > batch_bytes (nothing of that genome is read).
+ *                     Only genomes all of whose pairs fit below cap_pairs are
+ *                     checked.  The pairs of a genome that is not regular are
+ *                     unspecified but lie inside its bytes and inside the table.
+ * So a caller reads d_n and d_status back once and runs again with larger tables
+ * if d_n[1] > cap_lines or d_n[0] > cap_pairs; a batch of d_n[1] newlines and n
+ * genomes has at most d_n[1] / 4 + 2 n pairs.  d_scratch (8-byte aligned) holds
+ * kf_index_fastq_scratch_bytes(batch_bytes, n_genomes, cap_lines) bytes: 8 per
+ * table entry, 8 per 4 KiB block of the batch (plus 1/1024 of that for the
+ * scan's upper levels) and about 32 per genome.  Nothing is allocated and no
+ * workgroup waits for another: ten launches, the newline counts per 4 KiB block,
+ * a three-level scan (1,024 entries per workgroup and level, so batch_bytes <=
+ * 4 TiB and n_genomes <= 2^30), the positions, one thread per genome, the same
+ * scan over the genomes' pair counts, one thread per pair.  KF_EINVAL for
+ * n_genomes < 0, null or misaligned pointers and sizes past those limits,
+ * KF_ERANGE for a scratch that is too small -- before anything is launched.
+ * Asynchronous on `stream`. */
+uint64_t kf_index_fastq_scratch_bytes(uint64_t batch_bytes, int32_t n_genomes, uint64_t cap_lines);
+int kf_index_fastq(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n_genomes,
+                   uint64_t batch_bytes, uint64_t* d_excl, uint64_t cap_pairs, uint64_t cap_lines,
+                   uint64_t* d_n, uint32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
+                   void* stream);
 
 /* Count canonical k-mers of a batch of genomes already resident in HBM
  * (replaces `jellyfish count -C` + `jellyfish dump -c`, main.py:309-323).

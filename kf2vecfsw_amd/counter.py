@@ -75,10 +75,11 @@ class HostBatch:
     """Genomes packed back to back: genome g = data[off[g]:off[g+1]]."""
     data: torch.Tensor | None   # uint8, (pinned) host
     off: np.ndarray             # uint64 [n+1]
-    excl: np.ndarray | None     # uint64 [2*m] absolute [start, end) pairs; None: FASTA indexed on the device
+    excl: np.ndarray | None     # uint64 [2*m] absolute [start, end) pairs; None: indexed on the device
     names: list[str]
     dev_data: torch.Tensor | None = None   # the bytes already copied to the device (maybe on another stream)
     dev_event: object = None               # ... and the event that copy recorded
+    fastq: bool = False                    # excl None: every genome is FASTQ (kf_index_fastq), not FASTA
 
     @property
     def n(self) -> int:
@@ -89,7 +90,8 @@ class HostBatch:
         d = self.data.numpy()
         nl = int(np.count_nonzero(d[: int(self.off[-1])] == 10))
         excl = self.excl if self.excl is not None else np.concatenate(
-            [index_records(d[int(self.off[i]): int(self.off[i + 1])], N.KF_FMT_FASTA, int(self.off[i]))[0]
+            [index_records(d[int(self.off[i]): int(self.off[i + 1])],
+                           N.KF_FMT_FASTQ if self.fastq else N.KF_FMT_FASTA, int(self.off[i]))[0]
              for i in range(self.n)] or [np.zeros(0, np.uint64)])
         ex = int((excl[1::2] - excl[0::2]).sum()) if excl.size else 0
         return int(self.off[-1] - self.off[0]) - nl - ex
@@ -139,8 +141,9 @@ def pack_files(paths: Sequence[str], names: Sequence[str] | None = None, fmt: in
     `buf`: a caller-owned (pinned) buffer of at least the batch's bytes to read
     into instead of a fresh allocation (the caller makes sure no copy still reads it).
     index=False: a batch of FASTA files is not indexed here (excl None: to_device
-    finds the header lines on the device, kf_index_fasta); a batch with a FASTQ
-    file is indexed on the host all the same."""
+    finds the header lines on the device, kf_index_fasta), nor is a batch whose
+    non-empty files are all FASTQ (excl None and fastq set: kf_index_fastq); a
+    batch that mixes the two is indexed on the host all the same."""
     from concurrent.futures import ThreadPoolExecutor
     import time
     t0 = time.perf_counter()
@@ -162,8 +165,11 @@ def pack_files(paths: Sequence[str], names: Sequence[str] | None = None, fmt: in
         N.check(N.lib().kf_read_files(arr, len(enc), sz.ctypes.data, off.ctypes.data, d.ctypes.data,
                                       int(piece), int(nthr)), "kf_read_files")
 
+    def is_fastq(i: int) -> bool:
+        return fmt == N.KF_FMT_FASTQ or (fmt == N.KF_FMT_AUTO and sizes[i] > 0 and d[int(off[i])] == ord("@"))
+
     def on_host(i: int) -> bool:   # FASTQ (or index=True): the host index
-        return index or fmt == N.KF_FMT_FASTQ or (fmt == N.KF_FMT_AUTO and sizes[i] > 0 and d[int(off[i])] == ord("@"))
+        return index or is_fastq(i)
 
     def host_index(i: int):
         lo, sz = int(off[i]), sizes[i]
@@ -171,6 +177,8 @@ def pack_files(paths: Sequence[str], names: Sequence[str] | None = None, fmt: in
 
     if not any(on_host(i) for i in range(len(paths))):   # FASTA only: the device indexes it
         return HostBatch(data, off, None, list(names) if names else list(paths))
+    if not index and all(is_fastq(i) or sizes[i] == 0 for i in range(len(paths))):   # FASTQ only: likewise
+        return HostBatch(data, off, None, list(names) if names else list(paths), fastq=True)
     if pool is not None:
         excl = list(pool.map(host_index, range(len(paths))))
     elif threads > 1 and len(paths) > 1:
@@ -261,12 +269,52 @@ def index_on_device(data: torch.Tensor, off: torch.Tensor, n: int, nbytes: int) 
         cap = m
 
 
+def index_fastq_on_device(data: torch.Tensor, off: torch.Tensor, n: int, nbytes: int
+                          ) -> tuple[torch.Tensor, int, bool]:
+    """FASTQ records of a device batch (kf_index_fastq) on the current stream:
+    (pairs int64[2m] on the device, m, whether every genome is in the regular
+    four-line form -- if not, the pairs are not to be used).  One small
+    synchronising copy reads the two counts and the genomes' status words back;
+    tables that were too small are grown and the index run again."""
+    dev = data.device
+    s = _stream_ptr(dev)
+    L = N.lib()
+    # reads of 100 bases or more have a '\n' per ~55 bytes and a pair per ~220
+    cap_lines = nbytes // 32 + 4 * n + 4096
+    cap_pairs = nbytes // 128 + 2 * n + 4096
+    info = torch.empty(2 + (n + 1) // 2, dtype=torch.int64, device=dev)   # d_n[2], then the status words
+    while True:
+        need = int(L.kf_index_fastq_scratch_bytes(nbytes, n, cap_lines))
+        scratch = torch.empty(max(need // 8, 1), dtype=torch.int64, device=dev)
+        excl = torch.empty(max(2 * cap_pairs, 2), dtype=torch.int64, device=dev)
+        N.check(L.kf_index_fastq(data.data_ptr(), off.data_ptr(), n, nbytes, excl.data_ptr(), cap_pairs, cap_lines,
+                                 info.data_ptr(), info.data_ptr() + 16, scratch.data_ptr(), need, s), "kf_index_fastq")
+        h = info.cpu().numpy()
+        m, lines = int(h[0]), int(h[1])
+        if lines > cap_lines:   # the pairs were not counted: allow for as many as these lines can make
+            cap_lines, cap_pairs = lines, max(cap_pairs, lines // 4 + 2 * n + 1)
+            continue
+        if m > cap_pairs:
+            cap_pairs = m
+            continue
+        status = h[2:].view(np.uint32)[:n]
+        if (status == 2).any():
+            raise N.NativeError("kf_index_fastq: genome offsets must be non-decreasing and end at or below the batch")
+        return excl[: 2 * m], m, not status.any()
+
+
+# which record index each batch without a host index took in to_device
+INDEX_PATHS = {"fasta_device": 0, "fastq_device": 0, "fastq_host_fallback": 0}
+
+
 def to_device(hb: HostBatch, device: torch.device | str = "cuda") -> DeviceBatch:
     """Asynchronous H2D of a batch on the current stream.  The small offset and
     interval tables are staged through pinned memory too: a copy from pageable
     memory would block the host until the stream's earlier copies finish.  A
     batch packed without its record index (excl None) is indexed on the device
-    (index_on_device: one small synchronising copy)."""
+    (index_on_device, or index_fastq_on_device for a FASTQ batch: one small
+    synchronising copy).  A FASTQ batch with a genome that is not in the regular
+    four-line form is copied back and indexed by the host instead."""
     dev = torch.device(device)
     if hb.dev_data is not None:   # copied already (get_frequencies' readers, on a copy stream)
         cur = torch.cuda.current_stream(dev)
@@ -280,8 +328,21 @@ def to_device(hb: HostBatch, device: torch.device | str = "cuda") -> DeviceBatch
         pin = hb.data is None or hb.data.is_pinned()
         off = torch.from_numpy(hb.off.view(np.int64))
         off = (off.pin_memory() if pin else off).to(dev, non_blocking=pin)
+        nbytes = int(hb.off[-1])
         with torch.cuda.device(dev):
-            excl, m = index_on_device(data, off, hb.n, int(hb.off[-1]))
+            if not hb.fastq:
+                excl, m = index_on_device(data, off, hb.n, nbytes)
+                INDEX_PATHS["fasta_device"] += 1
+            else:
+                excl, m, regular = index_fastq_on_device(data, off, hb.n, nbytes)
+                INDEX_PATHS["fastq_device" if regular else "fastq_host_fallback"] += 1
+                if not regular:
+                    # from the device copy: the reader may be refilling hb.data (a pinned slot) already
+                    d = data[:nbytes].cpu().numpy()
+                    iv = np.concatenate([index_records(d[int(hb.off[i]): int(hb.off[i + 1])], N.KF_FMT_FASTQ,
+                                                       int(hb.off[i]))[0] for i in range(hb.n)])
+                    m = iv.size // 2
+                    excl = torch.from_numpy(iv.view(np.int64)).to(dev)
         return DeviceBatch(data, off, excl if m else torch.zeros(2, dtype=torch.int64, device=dev), hb.n, m)
     ex = hb.excl if hb.excl.size else np.zeros(2, np.uint64)
     pin = hb.data is None or hb.data.is_pinned()

@@ -346,8 +346,9 @@ def get_frequencies(args) -> None:
         j = bi % n_slots
         if slot_ev[j] is not None:
             slot_ev[j].synchronize()
-        # FASTA batches are indexed on the device (to_device -> kf_index_fasta):
-        # the readers only copy the files
+        # FASTA batches and all-FASTQ batches are indexed on the device (to_device
+        # -> kf_index_fasta / kf_index_fastq): the readers only copy the files.
+        # A batch that mixes the two is still indexed here, by the files' pool.
         hb = pack_files([paths[i] for i in idx], [samples_names[i] for i in idx], pool=files_pool, times=tm,
                         buf=slots[j], index=False)
         # the batch goes to the device on the copy stream as soon as it is read,
@@ -469,8 +470,10 @@ def get_frequencies(args) -> None:
             d = [round(base_cpu + e00.elapsed_time(x), 3) for x in e]
             tr.append(("gpu", bi, t_issue, {"h2d": d[:2], "count": d[1:3], "d2h": d[2:4]}))
         import json
+        from .counter import INDEX_PATHS   # which record index the batches took (this process, so far)
         print(json.dumps({"kf_trace": tr, "total_ms": now_ms(), "written_ms": t_written,
-                          "setup_ms": round((t_origin - t_entry) * 1e3, 3)}), file=sys.stderr)
+                          "setup_ms": round((t_origin - t_entry) * 1e3, 3), "index_paths": dict(INDEX_PATHS)}),
+              file=sys.stderr)
 
     _finish(args, shard, lead)
 
