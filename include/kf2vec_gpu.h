@@ -51,8 +51,8 @@ extern "C" {
 #define KF_MAX_K 12      /* dense device kernels; the CLI accepts 3..11 */
 #define KF_SPARSE_MAX_K 31  /* kf_sparse_count (get_kmers, main.py:81-82) */
 
-/* kf_count_batch flags */
-#define KF_ACCUMULATE 1u /* do not zero d_counts / d_totals first */
+/* kf_count_batch and kf_rows_accumulate flags */
+#define KF_ACCUMULATE 1u /* do not zero d_counts / d_totals first; add into the destination rows */
 
 /* input formats */
 #define KF_FMT_AUTO 0    /* sniff: first byte '@' -> FASTQ, else FASTA */
@@ -188,6 +188,40 @@ int kf_count_batch(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n_gen
                    const uint64_t* d_excl, uint64_t n_excl,
                    const uint32_t* d_code2col, const uint32_t* d_col2rep, int k,
                    uint32_t* d_counts, uint64_t* d_totals, uint32_t flags, void* stream);
+
+/* Column-wise sums of count rows on the device: what adds the rows of a file
+ * that get_frequencies counted in pieces (each piece one genome of a
+ * kf_count_batch) up into the file's row.  d_src is n_src x nbins uint32 with
+ * d_src_totals[n_src]; d_seg holds n_dst + 1 non-decreasing offsets into the
+ * source rows (the seg_row0 idiom of kf_write_kf_segments), and destination row
+ * r of d_dst (n_dst x nbins) receives the column-wise sum of the source rows
+ * [d_seg[r], d_seg[r+1]), d_dst_totals[r] the sum of their totals.
+ *   flags = 0             : the row, its total and d_status[r] are overwritten;
+ *                           an empty segment gives zeros, total 0, status 0
+ *   flags = KF_ACCUMULATE : the sum is added to what the row and its total hold
+ *                           and d_status[r] is OR-ed into, so a file's pieces may
+ *                           come in several calls; an empty segment leaves the
+ *                           row, its total and its status untouched
+ *   d_status[r] bit 0     : a column's true sum passed 2^32 - 1.  That column is
+ *                           stored as UINT32_MAX (so any later accumulating add
+ *                           to it carries again: the flag is sticky); a sum of
+ *                           exactly 2^32 - 1 is no overflow.  Errors are never
+ *                           silent: a caller reads the status before it uses
+ *                           the row.  The u64 totals are not checked.
+ *   d_status[r] == 2      : the segment table is bad -- an offset below 0 or
+ *                           above n_src, or a decrease.  Checked on the device;
+ *                           then nothing of d_dst or d_dst_totals is written and
+ *                           every status word is 2.
+ * d_dst must not overlap d_src.  Rows are read and written 16 bytes per thread
+ * when nbins % 4 == 0 and both matrices are 16-byte aligned (every k >= 3), else
+ * 4 bytes.  KF_EINVAL for a null or misaligned pointer, a negative count or
+ * nbins == 0, before anything is launched.  One launch (after a memset of the
+ * status words without KF_ACCUMULATE): asynchronous on `stream`, no allocation,
+ * no workgroup waits for another. */
+int kf_rows_accumulate(const uint32_t* d_src, const uint64_t* d_src_totals, int32_t n_src,
+                       const int32_t* d_seg, int32_t n_dst, uint64_t nbins,
+                       uint32_t* d_dst, uint64_t* d_dst_totals, uint32_t* d_status,
+                       uint32_t flags, void* stream);
 
 /* Allocate up front, on the current device, everything kf_count_batch(k, n)
  * needs for any n <= max_genomes: the k >= 10 bucket tables, workspace and

@@ -38,6 +38,7 @@ SIGNATURES = {
     "kf_vocab_text": (_int, [_int, _vp, _u64, _P64]),
     "kf_index_records": (_int, [_vp, _u64, _int, _u64, _vp, _u64, _P64, _PI]),
     "kf_count_batch": (_int, [_vp, _vp, _i32, _vp, _u64, _vp, _vp, _int, _vp, _vp, _u32, _vp]),
+    "kf_rows_accumulate": (_int, [_vp, _vp, _i32, _vp, _i32, _u64, _vp, _vp, _vp, _u32, _vp]),
     "kf_count_launch_info": (_int, [_int, _PI, _PI, _PI]),
     "kf_workspace_release": (_int, []),
     "kf_workspace_reserve": (_int, [_int, _i32]),

@@ -195,18 +195,27 @@ def pack_files(paths: Sequence[str], names: Sequence[str] | None = None, fmt: in
 
 
 def pack_ranges(ranges: Sequence[tuple[str, int, int]], names: Sequence[str] | None = None, pin: bool = True,
-                threads: int = 8, chunk: int = 64 << 20, index: bool = False) -> HostBatch:
+                threads: int = 8, chunk: int = 64 << 20, index: bool = False, buf: torch.Tensor | None = None,
+                fastq: bool = False) -> HostBatch:
     """As pack_files for byte ranges [(path, start, end)] of files (the pieces of
-    a file too large for one sparse call, main.fasta_pieces, or get_chunks'
-    record-aligned parts, main.record_pieces), read by os.preadv in chunks of
-    `chunk` bytes on `threads` threads; FASTA only (index=False: the record index
-    is left to the device; index=True: the header lines indexed here)."""
+    a file too large for one sparse call, main.fasta_pieces, get_chunks'
+    record-aligned parts, main.record_pieces, or get_frequencies' pieces of a
+    file above its split limit), read by os.preadv in chunks of `chunk` bytes on
+    `threads` threads.  FASTA (index=False: the record index is left to the
+    device; index=True: the header lines indexed here) unless `fastq`: then every
+    range is FASTQ that starts at a record start (main.fastq_pieces) and the
+    device indexes it (excl None and fastq set: kf_index_fastq).
+    `buf`: a caller-owned (pinned) buffer to read into, as pack_files takes."""
     from concurrent.futures import ThreadPoolExecutor
     sizes = [e - a for _, a, e in ranges]
     off = _layout(sizes)
-    data = _alloc_host(int(off[-1]), pin)
+    if buf is not None and buf.numel() >= max(int(off[-1]), ALIGN):
+        data = buf[: max(int(off[-1]), ALIGN)]
+    else:
+        data = _alloc_host(int(off[-1]), pin)
     d = data.numpy()
-    d[: int(off[-1])] = 10                       # '\n' padding is transparent
+    for i, sz in enumerate(sizes):                # '\n' padding is transparent
+        d[int(off[i]) + sz: int(off[i + 1])] = 10
     jobs = []
     for i, (p, a, e) in enumerate(ranges):
         for x in range(a, e, chunk):
@@ -229,11 +238,11 @@ def pack_ranges(ranges: Sequence[tuple[str, int, int]], names: Sequence[str] | N
     with ThreadPoolExecutor(max_workers=max(1, int(threads))) as ex:
         list(ex.map(read, jobs))
         excl = None
-        if index:
+        if index and not fastq:
             parts = list(ex.map(lambda i: index_records(d[int(off[i]): int(off[i]) + sizes[i]], N.KF_FMT_FASTA,
                                                         int(off[i]))[0], range(len(ranges))))
             excl = (np.concatenate(parts) if parts else np.zeros(0, np.uint64)).astype(np.uint64)
-    return HostBatch(data, off, excl, list(names) if names else [f"{p}:{a}" for p, a, _ in ranges])
+    return HostBatch(data, off, excl, list(names) if names else [f"{p}:{a}" for p, a, _ in ranges], fastq=fastq)
 
 
 @dataclasses.dataclass
@@ -243,6 +252,8 @@ class DeviceBatch:
     excl: torch.Tensor      # int64 [2m]
     n: int
     n_excl: int
+    irregular: tuple = ()   # to_device(fallback=False): the genomes of a FASTQ batch that kf_index_fastq found
+                            # not regular (their part of excl is not to be used: the caller refuses the batch)
 
 
 def index_on_device(data: torch.Tensor, off: torch.Tensor, n: int, nbytes: int) -> tuple[torch.Tensor, int]:
@@ -269,13 +280,14 @@ def index_on_device(data: torch.Tensor, off: torch.Tensor, n: int, nbytes: int) 
         cap = m
 
 
-def index_fastq_on_device(data: torch.Tensor, off: torch.Tensor, n: int, nbytes: int
+def index_fastq_on_device(data: torch.Tensor, off: torch.Tensor, n: int, nbytes: int, status_out: list | None = None
                           ) -> tuple[torch.Tensor, int, bool]:
     """FASTQ records of a device batch (kf_index_fastq) on the current stream:
     (pairs int64[2m] on the device, m, whether every genome is in the regular
     four-line form -- if not, the pairs are not to be used).  One small
     synchronising copy reads the two counts and the genomes' status words back;
-    tables that were too small are grown and the index run again."""
+    tables that were too small are grown and the index run again.  status_out: a
+    list that receives the genomes' status words (uint32[n])."""
     dev = data.device
     s = _stream_ptr(dev)
     L = N.lib()
@@ -300,6 +312,8 @@ def index_fastq_on_device(data: torch.Tensor, off: torch.Tensor, n: int, nbytes:
         status = h[2:].view(np.uint32)[:n]
         if (status == 2).any():
             raise N.NativeError("kf_index_fastq: genome offsets must be non-decreasing and end at or below the batch")
+        if status_out is not None:
+            status_out.append(status.copy())
         return excl[: 2 * m], m, not status.any()
 
 
@@ -307,14 +321,18 @@ def index_fastq_on_device(data: torch.Tensor, off: torch.Tensor, n: int, nbytes:
 INDEX_PATHS = {"fasta_device": 0, "fastq_device": 0, "fastq_host_fallback": 0}
 
 
-def to_device(hb: HostBatch, device: torch.device | str = "cuda") -> DeviceBatch:
+def to_device(hb: HostBatch, device: torch.device | str = "cuda", fallback: bool = True) -> DeviceBatch:
     """Asynchronous H2D of a batch on the current stream.  The small offset and
     interval tables are staged through pinned memory too: a copy from pageable
     memory would block the host until the stream's earlier copies finish.  A
     batch packed without its record index (excl None) is indexed on the device
     (index_on_device, or index_fastq_on_device for a FASTQ batch: one small
     synchronising copy).  A FASTQ batch with a genome that is not in the regular
-    four-line form is copied back and indexed by the host instead."""
+    four-line form is copied back and indexed by the host instead -- unless
+    fallback=False (the pieces of a file cut by main.fastq_pieces: a piece that
+    is not regular was cut at a wrong line, which the host index would read as
+    if it were a record start): then the batch comes back with those genomes
+    named in DeviceBatch.irregular, for the caller to refuse."""
     dev = torch.device(device)
     if hb.dev_data is not None:   # copied already (get_frequencies' readers, on a copy stream)
         cur = torch.cuda.current_stream(dev)
@@ -334,8 +352,12 @@ def to_device(hb: HostBatch, device: torch.device | str = "cuda") -> DeviceBatch
                 excl, m = index_on_device(data, off, hb.n, nbytes)
                 INDEX_PATHS["fasta_device"] += 1
             else:
-                excl, m, regular = index_fastq_on_device(data, off, hb.n, nbytes)
-                INDEX_PATHS["fastq_device" if regular else "fastq_host_fallback"] += 1
+                st: list = []
+                excl, m, regular = index_fastq_on_device(data, off, hb.n, nbytes, st)
+                INDEX_PATHS["fastq_device" if regular or not fallback else "fastq_host_fallback"] += 1
+                if not regular and not fallback:
+                    return DeviceBatch(data, off, excl if m else torch.zeros(2, dtype=torch.int64, device=dev), hb.n, m,
+                                       tuple(int(g) for g in np.flatnonzero(st[0])))
                 if not regular:
                     # from the device copy: the reader may be refilling hb.data (a pinned slot) already
                     d = data[:nbytes].cpu().numpy()
@@ -360,6 +382,30 @@ def to_device(hb: HostBatch, device: torch.device | str = "cuda") -> DeviceBatch
 
 def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def accumulate_rows(src: torch.Tensor, src_totals: torch.Tensor, seg: torch.Tensor, dst: torch.Tensor,
+                    dst_totals: torch.Tensor, status: torch.Tensor, accumulate: bool = False,
+                    stream: int | None = None) -> None:
+    """Enqueue kf_rows_accumulate: dst[r] (int32[n_dst, nbins] holding uint32 bit
+    patterns, as KmerCounter.count gives) receives the column-wise sum of the rows
+    src[seg[r]: seg[r + 1]] (seg int32[n_dst + 1] on the device), dst_totals[r]
+    the sum of their totals, added to what they hold if `accumulate`.  status
+    (int32[n_dst]) bit 0: a column passed 2^32 - 1 and holds UINT32_MAX; 2: the
+    segment table is bad and nothing was written.  The caller reads status back
+    before it uses the rows."""
+    assert src.dtype == torch.int32 and dst.dtype == torch.int32 and src.is_contiguous() and dst.is_contiguous()
+    assert src.dim() == 2 and dst.dim() == 2 and src.shape[1] == dst.shape[1]
+    assert src_totals.dtype == torch.int64 and src_totals.shape == (src.shape[0],) and src_totals.is_contiguous()
+    assert dst_totals.dtype == torch.int64 and dst_totals.shape == (dst.shape[0],) and dst_totals.is_contiguous()
+    assert seg.dtype == torch.int32 and seg.shape == (dst.shape[0] + 1,) and seg.is_contiguous()
+    assert status.dtype == torch.int32 and status.shape == (dst.shape[0],) and status.is_contiguous()
+    s = _stream_ptr(dst.device) if stream is None else stream
+    with torch.cuda.device(dst.device):
+        N.check(N.lib().kf_rows_accumulate(src.data_ptr(), src_totals.data_ptr(), src.shape[0], seg.data_ptr(),
+                                           dst.shape[0], dst.shape[1], dst.data_ptr(), dst_totals.data_ptr(),
+                                           status.data_ptr(), N.KF_ACCUMULATE if accumulate else 0, s),
+                "kf_rows_accumulate")
 
 
 _DEV_TABLES: dict = {}   # (k, device index) -> (code2col, col2rep) on the device

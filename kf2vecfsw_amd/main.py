@@ -113,6 +113,56 @@ def _size_batches(sizes: list[int], budget: int, ramp: bool = False, max_files: 
     return out
 
 
+def _plan_units(sizes: list[int], pieces: list | None, budget: int, max_units: int | None = None,
+                ramp: bool = True) -> list[list[tuple[int, int, int, str]]]:
+    """get_frequencies' batches as lists of units (file index, start, end, kind):
+    a whole file (kind "whole") or, for a file i with pieces[i] = (kind, [(start,
+    end), ...]), kind "fasta" or "fastq", each of its pieces.  Consecutive units in
+    batches as _size_batches makes them -- at most `budget` bytes (a larger unit
+    alone; ramp: a quarter and a half of it for the first two) and at most
+    `max_units` units, a piece counting as a genome -- and a batch holds whole
+    files only or pieces of one kind only.  So a batch is at most max(budget,
+    largest unit) bytes whatever the file sizes, and with no pieces the batches
+    are _size_batches' own.  A pure function of its arguments."""
+    out, cur, size = [], [], 0
+    for fi, s in enumerate(sizes):
+        pcs = pieces[fi] if pieces is not None else None
+        for u in ([(fi, 0, s, "whole")] if not pcs else [(fi, a, e, pcs[0]) for a, e in pcs[1]]):
+            lim = budget >> max(0, 2 - len(out)) if ramp else budget
+            if cur and (size + u[2] - u[1] > lim or (max_units is not None and len(cur) >= max_units)
+                        or u[3] != cur[-1][3]):
+                out.append(cur)
+                cur, size = [], 0
+            cur.append(u)
+            size += u[2] - u[1]
+    if cur:
+        out.append(cur)
+    return out
+
+
+SPLIT_GB = 4.0   # get_frequencies -split_gb: the upper clamp of _pipeline_budget
+
+
+def _split_pieces(paths: list[str], sizes: list[int], k: int, split_gb) -> list | None:
+    """_plan_units' `pieces` for get_frequencies: a file above -split_gb S GiB is
+    cut into pieces of about min(S, 1) GiB -- fastq_pieces if its first byte is
+    '@' (the sniff of KF_FMT_AUTO), else fasta_pieces -- unless no cut was found
+    (one piece: the file is counted whole).  None if no file is cut."""
+    s = float(SPLIT_GB if split_gb is None else split_gb)
+    if s <= 0:
+        return None
+    limit, piece = int(s * (1 << 30)), int(min(s, 1.0) * (1 << 30))
+    out: list = [None] * len(paths)
+    for i, (p, sz) in enumerate(zip(paths, sizes)):
+        if sz > limit:
+            with open(p, "rb") as f:
+                fq = f.read(1) == b"@"
+            pcs = fastq_pieces(p, piece) if fq else fasta_pieces(p, k, piece)
+            if len(pcs) > 1:
+                out[i] = ("fastq" if fq else "fasta", pcs)
+    return out if any(o is not None for o in out) else None
+
+
 def shard_files(sizes: list[int], samples: list[str], world: int) -> list[list[int]]:
     """Byte-balanced shards of the input files for `world` GPUs (section 8(e): genomes
     are independent, no collective).  Files of one sample name stay in one shard,
@@ -292,7 +342,7 @@ def get_frequencies(args) -> None:
             args.k, supported_k.start, supported_k.stop - 1))
 
     import torch
-    from .counter import KmerCounter, pack_files, to_device
+    from .counter import KmerCounter, accumulate_rows, pack_files, pack_ranges, to_device
 
     if shard is not None and not os.environ.get("KF_SHARD"):
         # torchrun: join the host-only gloo group now, before counting, so that a
@@ -312,9 +362,12 @@ def get_frequencies(args) -> None:
     # device, pinned for the writer, `behind` batches deep) stays bounded at any k
     batch_gb = getattr(args, "batch_gb", None)
     fsz = [os.path.getsize(p) for p in paths]
-    asz = [(x + 15) // 16 * 16 for x in fsz]   # bytes in a batch (16-byte aligned files)
-    batches = _size_batches(fsz, _pipeline_budget(paths, batch_gb, fsz), ramp=True,
-                            max_files=_count_cap(4 * counter.nbins, batch_gb))
+    # a file above -split_gb goes through the same stages in pieces, each piece one
+    # genome of a batch, its rows summed on the device into one row per file
+    # (kf_rows_accumulate): no batch, pinned slot or device block grows with a file
+    batches = _plan_units(fsz, _split_pieces(paths, fsz, args.k, getattr(args, "split_gb", SPLIT_GB)),
+                          _pipeline_budget(paths, batch_gb, fsz), _count_cap(4 * counter.nbins, batch_gb))
+    last_unit = {u[0]: (bi, j) for bi, b in enumerate(batches) for j, u in enumerate(b)}   # a file's last piece
     # the reference processes files in order and later ones overwrite earlier
     # ones with the same sample name: keep the last occurrence only
     last = {s: i for i, s in enumerate(samples_names)}
@@ -335,22 +388,27 @@ def get_frequencies(args) -> None:
     # pinned input slots, reused round robin (a fresh pinned block per batch costs
     # ~1 ms of allocation on the reader's path): batch i reads into slot i mod
     # n_slots once the H2D that last read that slot has completed
-    slot_bytes = max(sum(asz[i] for i in b) for b in batches)
+    slot_bytes = max(sum((e - a + 15) // 16 * 16 for _, a, e, _ in b) for b in batches)   # 16-byte aligned units
     n_slots = min(len(batches), int(os.environ.get("KF_READ_AHEAD", "2")) + 2)
     slots = [torch.empty(max(slot_bytes, 16), dtype=torch.uint8, pin_memory=True) for _ in range(n_slots)]
     slot_ev: list = [None] * n_slots
 
-    def pack(bi, idx):
+    def pack(bi, units):
         t0 = now_ms()
         tm = {}
         j = bi % n_slots
+        idx = [u[0] for u in units]
         if slot_ev[j] is not None:
             slot_ev[j].synchronize()
         # FASTA batches and all-FASTQ batches are indexed on the device (to_device
         # -> kf_index_fasta / kf_index_fastq): the readers only copy the files.
         # A batch that mixes the two is still indexed here, by the files' pool.
-        hb = pack_files([paths[i] for i in idx], [samples_names[i] for i in idx], pool=files_pool, times=tm,
-                        buf=slots[j], index=False)
+        if units[0][3] == "whole":
+            hb = pack_files([paths[i] for i in idx], [samples_names[i] for i in idx], pool=files_pool, times=tm,
+                            buf=slots[j], index=False)
+        else:   # pieces of one kind: always indexed on the device
+            hb = pack_ranges([(paths[i], a, e) for i, a, e, _ in units], [samples_names[i] for i in idx],
+                             threads=threads, buf=slots[j], fastq=units[0][3] == "fastq")
         # the batch goes to the device on the copy stream as soon as it is read,
         # so its H2D overlaps the previous batch's index, count and copy-back
         # (copies issued while the batch is read, 16 MiB at a time from the
@@ -404,16 +462,61 @@ def get_frequencies(args) -> None:
     # pinned count matrix (4 x bins B per genome), so the backlog is bounded
     behind = max(1, int(os.environ.get("KF_WRITE_BEHIND", "2")))
 
-    def write(ev, host, names):
+    def write(ev, host, names, hstat=None, fnames=None):
         ev.synchronize()
         t0 = now_ms()
         c = host.numpy().view(np.uint32)
+        for j in range(0 if hstat is None else len(fnames)):   # files counted in pieces: the sums' status words
+            st = int(hstat[j])
+            if st & 1:
+                raise ValueError("{}: a k-mer count passed 2^32 - 1 when the file's pieces were summed "
+                                 "(uint32 counts): nothing was written for it".format(fnames[j]))
+            if st:
+                raise N.NativeError("kf_rows_accumulate: bad segment table ({})".format(fnames[j]))
         write_kf_files(args.output_dir, names, c, args.pseudocount, args.raw_cnt, threads)
         if trace:
             tr.append(("write", names[0] if names else "", t0, now_ms()))
 
+    def stop():
+        """Before an error is raised from this thread: nothing more is read, and
+        what was handed to the writer is written."""
+        for f in reads:
+            f.cancel()
+        reader.shutdown()
+        writer.shutdown()
+        files_pool.shutdown()
+
+    # a file counted in pieces: its row, total and status on the device from its
+    # first piece until its last one is counted (its pieces may span batches)
+    acc: dict = {}
+    seg_of: dict = {}   # n -> the segment table [0, n] on the device
+
+    def fold(bi, units, counts, totals):
+        """Adds a piece batch's rows into their files' accumulator rows
+        (kf_rows_accumulate, one call per file in the batch); returns the files
+        whose last piece this batch holds."""
+        done, j = [], 0
+        while j < len(units):
+            fi, j1 = units[j][0], j + 1
+            while j1 < len(units) and units[j1][0] == fi:
+                j1 += 1
+            if fi not in acc:
+                acc[fi] = (torch.zeros((1, counter.nbins), dtype=torch.int32, device=device),
+                           torch.zeros(1, dtype=torch.int64, device=device),
+                           torch.zeros(1, dtype=torch.int32, device=device))
+            if j1 - j not in seg_of:
+                seg_of[j1 - j] = torch.tensor([0, j1 - j], dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+            accumulate_rows(counts[j:j1], totals[j:j1], seg_of[j1 - j], *acc[fi], accumulate=True,
+                            stream=stream.cuda_stream)
+            if last_unit[fi] == (bi, j1 - 1):
+                done.append(fi)
+            j = j1
+        return done
+
     evs = []
-    for bi, idx in enumerate(batches):
+    for bi, units in enumerate(batches):
+        idx = [u[0] for u in units]
+        whole = units[0][3] == "whole"
         t_wait = now_ms()
         hb = reads.popleft().result()
         if trace:
@@ -425,17 +528,40 @@ def get_frequencies(args) -> None:
                 e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
                 e[0].record(stream)
                 evs.append((bi, now_ms(), e))
-            db = to_device(hb, device)
+            # a FASTQ piece that is not regular was cut at a wrong line: the host
+            # index would count it as if it were well cut, so it is refused instead
+            db = to_device(hb, device, fallback=whole)
             del hb
+            if db.irregular:
+                fi, a = units[db.irregular[0]][:2]
+                stop()
+                raise ValueError("{}: the piece at byte {} is not FASTQ in the regular four-line form (a cut at a "
+                                 "line that is no record start, or a malformed file): -split_gb 0 counts the file "
+                                 "whole".format(files_names[fi], a))
             if trace:
                 e[1].record(stream)
                 th = [now_ms()]
-            counts, _ = counter.count(db, stream=stream.cuda_stream)
+            counts, totals = counter.count(db, stream=stream.cuda_stream)
             if trace:
                 e[2].record(stream)
                 th.append(now_ms())
-            keep = [j for j, i in enumerate(idx) if last[samples_names[i]] == i]
-            rows = counts if len(keep) == len(idx) else counts[torch.tensor(keep, device=device)]
+            hstat = None
+            if whole:
+                done = idx
+                keep = [j for j, i in enumerate(idx) if last[samples_names[i]] == i]
+                kept = [idx[j] for j in keep]
+                # (int64 named: a batch of which no file is kept -- a whole file ahead of the pieces of a
+                # later file with its sample name -- gives an empty index list)
+                rows = counts if len(keep) == len(idx) else counts[torch.tensor(keep, dtype=torch.int64, device=device)]
+            else:
+                done = fold(bi, units, counts, totals)
+                kept = [fi for fi in done if last[samples_names[fi]] == fi]
+                rows = torch.cat([acc[fi][0] for fi in kept]) if kept else counts[:0]
+                if kept:
+                    hstat = torch.empty(len(kept), dtype=torch.int32, pin_memory=True)
+                    hstat.copy_(torch.cat([acc[fi][2] for fi in kept]), non_blocking=True)
+                for fi in done:
+                    del acc[fi]
             host = torch.empty(rows.shape, dtype=rows.dtype, pin_memory=True)
             if trace:
                 th.append(now_ms())
@@ -445,15 +571,16 @@ def get_frequencies(args) -> None:
             if trace:
                 e[3].record(stream)
                 th.append(now_ms())
-        for i in idx:
+        for i in done:   # a file counted in pieces: once, with its last piece
             if args.pseudocount:                       # main.py:332-333
                 print(">>> Adding pseudocounts. Sample: {}".format(files_names[i]))
             if not args.raw_cnt:                       # main.py:340-341
                 print(">>> Normalizing. Sample: {}".format(files_names[i]))
         if bi >= behind:   # backpressure: at most `behind` batches queued for the writer
             writes[bi - behind].result()
-        writes.append(writer.submit(write, ev, host, [samples_names[idx[j]] for j in keep]))
-        del host, rows, counts, db
+        writes.append(writer.submit(write, ev, host, [samples_names[i] for i in kept], hstat,
+                                    [files_names[i] for i in kept]))
+        del host, rows, counts, totals, db
         if trace:
             th.append(now_ms())
             tr.append(("issue", bi, th))   # after: to_device, count, pinned alloc, D2H, prints+submit
@@ -472,7 +599,8 @@ def get_frequencies(args) -> None:
         import json
         from .counter import INDEX_PATHS   # which record index the batches took (this process, so far)
         print(json.dumps({"kf_trace": tr, "total_ms": now_ms(), "written_ms": t_written,
-                          "setup_ms": round((t_origin - t_entry) * 1e3, 3), "index_paths": dict(INDEX_PATHS)}),
+                          "setup_ms": round((t_origin - t_entry) * 1e3, 3), "index_paths": dict(INDEX_PATHS),
+                          "pinned_slots": [n_slots, slot_bytes]}),
               file=sys.stderr)
 
     _finish(args, shard, lead)
@@ -511,6 +639,8 @@ def _child_argv(args) -> list[str]:
         a.append("-raw_cnt")
     if getattr(args, "batch_gb", None):
         a += ["-batch_gb", str(args.batch_gb)]
+    if getattr(args, "split_gb", None) is not None:
+        a += ["-split_gb", repr(float(args.split_gb))]
     return a
 
 
@@ -663,6 +793,71 @@ def fasta_pieces(path: str, k: int, piece: int = SPLIT_BYTES) -> list[tuple[int,
                 for i, c in enumerate(cuts)]
     finally:
         os.close(fd)
+
+
+def _next_nl(fd: int, pos: int, size: int) -> int:
+    """Offset of the first '\\n' at or after pos, or size if there is none."""
+    step = 1 << 10
+    while pos < size:
+        blk = os.pread(fd, min(step, size - pos), pos)
+        if not blk:
+            break
+        j = blk.find(b"\n")
+        if j >= 0:
+            return pos + j
+        pos += len(blk)
+        step = min(step << 2, 1 << 20)
+    return size
+
+
+def _fastq_cut(fd: int, s: int, limit: int, size: int) -> int | None:
+    """The first line start L in [s, limit) that fastq_pieces accepts as a record
+    start, or None."""
+    L = s if s == 0 or os.pread(fd, 1, s - 1) == b"\n" else _next_nl(fd, s, size) + 1
+    while L < min(limit, size):
+        e0 = _next_nl(fd, L, size)                 # line L = [L, e0)
+        if os.pread(fd, 1, L) == b"@":
+            e1 = _next_nl(fd, e0 + 1, size)        # line L+1 = [e0 + 1, e1)
+            if e1 + 1 < size and os.pread(fd, 1, e1 + 1) == b"+":
+                s3 = _next_nl(fd, e1 + 1, size) + 1
+                if s3 >= size or _next_nl(fd, s3, size) - s3 >= e1 - (e0 + 1):
+                    return L
+        L = e0 + 1
+    return None
+
+
+def fastq_pieces(path: str, piece: int = SPLIT_BYTES) -> list[tuple[int, int]]:
+    """Byte ranges [(a_i, e_i)] that tile a FASTQ file in the regular four-line
+    form (include/kf2vec_gpu.h, kf_index_fastq) in pieces of about `piece` bytes,
+    each starting at a record's header line: k-mers never span records, so the
+    pieces' counts sum to the file's and no overlap is needed.  A start other
+    than 0 is the first line L at or after a multiple of `piece` (and before the
+    next one: else the two pieces stay one) such that
+      - L starts with '@',
+      - line L+2 starts with '+',
+      - line L+3 is at least as long as line L+1 (lengths without the '\\n'; not
+        asked if the file ends before line L+3).
+    Every header line followed by a whole record passes.  A quality line that
+    starts with '@' does not: two lines on is a sequence line, which in the
+    regular form never starts with '+'.  What remains is a sequence line that
+    starts with '@' whose quality line starts with '+': a piece cut there starts
+    with a sequence line and has its '+' line where a sequence line belongs, so
+    the device index reads it as not regular and get_frequencies refuses the
+    file, never counts it wrongly.
+    A file with no acceptable cut (multi-line records) is one piece."""
+    size = os.path.getsize(path)
+    if size <= piece:
+        return [(0, size)]
+    cuts = [0]
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        for i in range(1, -(-size // piece)):
+            c = _fastq_cut(fd, i * piece, (i + 1) * piece, size)
+            if c is not None and c < size:
+                cuts.append(c)
+    finally:
+        os.close(fd)
+    return [(c, cuts[i + 1] if i + 1 < len(cuts) else size) for i, c in enumerate(cuts)]
 
 
 def _next_record(fd: int, pos: int, size: int) -> int:
@@ -1059,6 +1254,9 @@ def build_parser() -> argparse.ArgumentParser:
     pf.add_argument("-raw_cnt", action="store_true", help="Computes raw k-mer counts without normalization")
     pf.add_argument("-batch_gb", type=float, default=None,
                     help="Input bytes per device batch (GiB). Default: about a quarter of the input, 16 MiB..4 GiB")
+    pf.add_argument("-split_gb", type=float, default=SPLIT_GB,
+                    help="A file larger than this (GiB) is counted in pieces of about min(this, 1) GiB, summed on "
+                         "the device, so no batch grows with a file. 0 never splits. Default: {:g}".format(SPLIT_GB))
     pf.add_argument("-device", default=None, help="torch device (default: cuda)")
     pf.add_argument("-gpus", type=int, default=1,
                     help="GPUs to shard the files over, one process each (0 = every visible GPU). Default: 1. "
