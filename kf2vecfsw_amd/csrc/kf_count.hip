@@ -73,6 +73,13 @@ struct XL {
     static constexpr uint32_t bytes = P + S;                                      // dynamic LDS of the kernel
 };
 constexpr int kXChunk = 3 * kChunk;                    // bytes per wave iteration
+static_assert((uint32_t)kXChunk == kLattice, "wave ranges are split on the iteration lattice (split_at_lattice)");
+// Pieces of up to this many iterations (7.5 MiB) take the lattice split.  Measured
+// at k = 7 on the same 5.06 GB (profiles/r07/lever_sweep.txt): the lattice saves
+// 2-3 % with genomes of up to 7 Mbp, nothing at 10 Mbp, and costs 3-5 % with
+// genomes of 20 Mbp and more (pieces of 10 MB and more), where the fixed cost per
+// piece is below 1 % of the piece anyway.  The cause of that loss is not known.
+constexpr uint32_t kLatticeMaxIters = 2560;
 // u16 exactness (xc_fast): k = 7 checks every add's return against 0x4000 and
 // moves 0x4000 at a time; k = 8 (48 adds per lane per iteration) against 0x2000;
 // k <= 6 (small tables, frequent crossings) against 0x8000: a half then stays
@@ -514,10 +521,11 @@ __device__ __forceinline__ uint32_t x_singles(const uint4 d, const CountArgs& A,
 
 // The wave range [lo, hi) of genome [glo, ghi) in 3 KiB iterations (K1x).
 // `drained` is set if a u16 half of this range was moved to the count row (the
-// flush then adds with atomics).
+// flush then adds with atomics).  `iv_hint`: the wave's interval cursor at the
+// start of its previous range (Range::warm16).
 template <int K>
 __device__ __forceinline__ uint32_t x_range(const CountArgs& A, int32_t g, uint64_t glo, uint64_t ghi, uint64_t lo,
-                                            uint64_t hi, int lane, uint32_t& drained) {
+                                            uint64_t hi, int lane, uint64_t& iv_hint, uint32_t& drained) {
     if (lo >= hi) return 0;
     uint32_t* gcounts = A.counts + (uint64_t)g * A.nbins;
     Range rg;
@@ -539,7 +547,7 @@ __device__ __forceinline__ uint32_t x_range(const CountArgs& A, int32_t g, uint6
         for (int j = 0; j < kXRing; ++j) buf[j] = load(j * kXChunk);
     }
     const uint32_t nx = (rg.nch + 2) / 3;   // 3 KiB iterations
-    rg.warm16<K>(A, lane);
+    rg.warm16<K>(A, lane, iv_hint);
     __builtin_amdgcn_s_setprio(0);   // (the setup ran at top priority, see k1x_kernel)
     uint32_t carry = rg.carry;
     uint32_t rel = 0;
@@ -647,6 +655,23 @@ __device__ __forceinline__ void pair_f_sums_small(const uint32_t* hist, int tid,
     }
 }
 
+// Zero the 16-byte units [lo4, hi4) of the table (1024 threads).  The k <= 7
+// flush zeroes in two steps, each in the phase after the last read of its words:
+//   barrier 1 (adds done)       -> P and S are read into registers (F sums)
+//   barrier 2 (P and S read)    -> F and the drain flags are written to words
+//                                  [0, 4^k + 16); every word past them is dead
+//                                  and zeroed in the same phase
+//   barrier 3 (F, flags written)-> the columns and the flags are read
+//   barrier 4 (columns read)    -> F's words and the flags are zeroed
+//   barrier 5 (end of piece)    -> both zeroings are done: every wave finds P and S
+//                                  zero before its next add
+// No barrier can go: F overwrites words that other threads read for their sums
+// (2), is read across threads (3) and zeroed under its readers (4).
+__device__ __forceinline__ void lds_zero(uint32_t* hist, uint32_t lo4, uint32_t hi4, int tid) {
+    uint4* h4 = (uint4*)hist;
+    for (uint32_t i = lo4 + (uint32_t)tid; i < hi4; i += kBlock) h4[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 template <int K>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) k1x_kernel(CountArgs A) {
     static_assert(K >= 2 && K <= 9, "K1x serves k = 2 .. 9 (k = 9: K9b byte counters)");
@@ -668,17 +693,28 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
     int32_t g = (int32_t)wave_upper_bound((uint64_t)A.n_genomes, span_lo, lane,
                                           [&](uint64_t i) { return A.goff[i + 1]; });
     const uint32_t fr_lo = wave_frac((uint32_t)wave, kWaveWeights), fr_hi = wave_frac((uint32_t)wave + 1, kWaveWeights);
+    // A piece's bounds one piece ahead (scalar loads): goff[g + 1] of a piece is
+    // goff[g] of the next, and goff[g + 2] is asked for a whole piece before its
+    // first use, so no piece after the first waits for its bounds.
+    uint64_t g_lo = A.goff[g], g_hi = A.goff[g + 1];
+    uint64_t iv_hint = 0;   // this wave's interval cursor at the start of its previous range
     for (; g < A.n_genomes; ++g) {
-        // a piece's setup (bounds, interval search, warm-up: dependent loads) at
-        // top priority, so the youngest wave slots do not start late
+        // a piece's setup (interval search, warm-up: dependent loads) at top
+        // priority, so the youngest wave slots do not start late
         __builtin_amdgcn_s_setprio(3);
-        const uint64_t glo = A.goff[g], ghi = A.goff[g + 1];
+        const uint64_t glo = g_lo, ghi = g_hi;
+        g_lo = g_hi;
+        g_hi = A.goff[min(g + 2, A.n_genomes)];
         if (glo >= span_hi) break;
         const uint64_t plo = max(glo, span_lo), phi = min(ghi, span_hi);
         if (phi <= plo) continue;
-        const uint64_t lo = split_at_frac(plo, phi, fr_lo), hi = split_at_frac(plo, phi, fr_hi);
+        // wave ranges on the 3 KiB lattice of wave 0's walk (split_at_lattice), up
+        // to kLatticeMaxIters iterations; a longer piece is split as before
+        const uint32_t nit = lattice_iters(plo, phi);
+        const bool lat = nit <= kLatticeMaxIters;
+        const uint64_t lo = split_at_lattice(plo, phi, nit, lat, fr_lo), hi = split_at_lattice(plo, phi, nit, lat, fr_hi);
         uint32_t drained = 0;   // plain row stores unless a half was drained
-        unsigned long long s = x_range<K>(A, g, glo, ghi, lo, hi, lane, drained);
+        unsigned long long s = x_range<K>(A, g, glo, ghi, lo, hi, lane, iv_hint, drained);
         uint32_t* gc = A.counts + (uint64_t)g * A.nbins;
         // A whole genome in this span (the common case) with no drained half: no
         // other workgroup and nothing else touches row g, which the caller
@@ -740,6 +776,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
             // [0, 4^k) (swizzled as f_swz), the drain flags after them
             constexpr uint32_t NY = 1u << (2 * K), NM = (NY + kBlock - 1) / kBlock;
             constexpr uint32_t NCOL = (NY + (K % 2 == 0 ? (1u << K) : 0u)) / 2, NC = (NCOL + kBlock - 1) / kBlock;
+            constexpr uint32_t ZF = (NY + 16) / 4;   // 16-byte units of F and the 16 drain flags
+            static_assert(ZF <= XL<K>::bytes / 16, "F and the flags lie inside the table");
             uint32_t rep[NC];
 #pragma unroll
             for (uint32_t c = 0; c < NC; ++c) {
@@ -756,6 +794,9 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
                 if (y < NY) hist[f_swz(y)] = F[m];
             }
             if (lane == 0) hist[NY + wave] = drained;   // (P holds 2 x 4^k words: past F is free)
+            // every word past F and the flags was read before the last barrier and
+            // is not touched again: zeroed here, off the end of the flush
+            lds_zero(hist, ZF, XL<K>::bytes / 16, tid);
             lds_barrier();   // F in LDS words [0, 4^k), drain flags after it
             const uint4* fl = (const uint4*)(hist + NY);
             const uint4 f0 = fl[0], f1 = fl[1], f2 = fl[2], f3 = fl[3];
@@ -767,9 +808,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
                 const uint32_t y = rep[c], rc = kf_revcomp<K>(y);
                 cv[c] = hist[f_swz(y)] + (rc != y ? hist[f_swz(rc)] : 0u);
             }
-            lds_barrier();   // columns read
-            uint4* h4 = (uint4*)hist;
-            for (uint32_t i = tid; i < XL<K>::bytes / 16; i += kBlock) h4[i] = make_uint4(0u, 0u, 0u, 0u);
+            lds_barrier();   // columns and flags read: F's words can go
+            lds_zero(hist, 0, ZF, tid);
 #pragma unroll
             for (uint32_t c = 0; c < NC; ++c) {
                 const uint32_t col = (uint32_t)tid + c * kBlock;
@@ -806,6 +846,11 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
 #pragma unroll
             for (int i = 0; i < 8; ++i) *(uint2*)(hist + f_swz(i * 2048 + 2 * tid)) = make_uint2(F[2 * i], F[2 * i + 1]);
             if (lane == 0) hist[16384 + wave] = drained;   // (words past F are free now)
+            // the upper half of P and all of S (96 KiB less the flags) were read
+            // before the last barrier and are not touched again: zeroed here, so
+            // only F's 64 KiB are left for the end of the flush
+            constexpr uint32_t ZF = (16384 + 16) / 4;   // 16-byte units of F and the 16 drain flags
+            lds_zero(hist, ZF, XL<K>::bytes / 16, tid);
             lds_barrier();   // F in LDS words [0, 16384), drain flags after it
             const uint4* fl = (const uint4*)(hist + 16384);
             const uint4 f0 = fl[0], f1 = fl[1], f2 = fl[2], f3 = fl[3];
@@ -817,9 +862,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
                 const uint32_t y = rep[c], rc = kf_revcomp<7>(y);
                 cv[c] = hist[f_swz(y)] + hist[f_swz(rc)];
             }
-            lds_barrier();   // columns read
-            uint4* h4 = (uint4*)hist;
-            for (uint32_t i = tid; i < XL<K>::bytes / 16; i += kBlock) h4[i] = make_uint4(0u, 0u, 0u, 0u);
+            lds_barrier();   // columns and flags read: F's words can go
+            lds_zero(hist, 0, ZF, tid);
             // the row writes last: their issue overlaps the zeroing, the barrier
             // and the next piece's setup
             if (whole && !any_drain) {

@@ -280,6 +280,41 @@ __device__ __forceinline__ uint64_t wave_upper_bound(uint64_t n, uint64_t x, int
     return a + (uint64_t)__builtin_popcountll(__ballot(i < b && key(i) <= x));
 }
 
+// First excluded interval that ends after x, with its bounds (s = e = ~0 and
+// iv = n_excl if none), from a lower bound `hint` of the answer (every interval
+// below `hint` ends at or before x).  One coalesced round of loads covers the 64
+// intervals from `hint`: lane L loads both bounds of interval hint + L, so the
+// answer's bounds come out of the same round by readlane; only an answer past
+// that window takes the search over the rest and two more dependent loads.
+struct IvHit {
+    uint64_t iv, s, e;
+};
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t l) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)l) << 32) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
+}
+__device__ __forceinline__ IvHit interval_after(const CountArgs& A, uint64_t x, uint64_t hint, int lane) {
+    const uint64_t i = hint + (uint64_t)lane;
+    uint64_t s = ~0ull, e = ~0ull;
+    if (i < A.n_excl) s = A.excl[2 * i], e = A.excl[2 * i + 1];
+    const uint32_t cnt = (uint32_t)__builtin_popcountll(__ballot(e <= x));   // (ends are sorted: the low lanes)
+    IvHit r;
+    if (cnt < (uint32_t)kWave) {
+        r.iv = hint + cnt;
+        r.s = readlane64(s, cnt);
+        r.e = readlane64(e, cnt);
+        return r;
+    }
+    const uint64_t a = hint + kWave;
+    r.iv = a + wave_upper_bound(A.n_excl - a, x, lane, [&](uint64_t j) { return A.excl[2 * (a + j) + 1]; });
+    r.s = r.e = ~0ull;
+    if (r.iv < A.n_excl) {
+        r.s = uload64(A.excl + 2 * r.iv);
+        r.e = uload64(A.excl + 2 * r.iv + 1);
+    }
+    return r;
+}
+
 // Lane block of the 1 KiB chunk at p for chunk_tail_data (bytes before the
 // genome's aligned start read as zero, so p may lie before the buffer).
 __device__ __forceinline__ uint4 chunk_tail_load(const uint8_t* bytes, int64_t p, uint64_t glo, int lane) {
@@ -362,31 +397,48 @@ struct Range {
     // case: they lie inside the genome, outside every excluded interval, and end
     // in >= k-1 bases); anything else takes warm.  Same carry as warm for every
     // use (codes of the last k-1 entries, a run of >= k-1).
+    // `hint`: a lower bound of the interval searches (interval_after), the cursor
+    // this wave found at the START of its previous range of the kernel (0 for its
+    // first).  A wave's ranges move forward through the batch, so the positions
+    // searched (p16 <= c0 of a range <= p16 of the next) never decrease and the
+    // last answer is a lower bound of the next; the cursor a range has ADVANCED
+    // to is none (it can pass the next genome's header).  Updated to the answer.
     template <int K>
-    __device__ __forceinline__ void warm16(const CountArgs& A, int lane) {
+    __device__ __forceinline__ void warm16(const CountArgs& A, int lane, uint64_t& hint) {
         if (c0 < glo + 16) {   // the genome start is within reach
-            warm<K>(A, lane);
+            warm_hinted<K>(A, lane, hint);
             return;
         }
         const uint64_t p16 = c0 - 16;
         const uint4 d = *(const uint4*)(A.bytes + p16);   // the same 16 bytes in every lane
-        uint64_t s_iv = ~0ull, e_iv = ~0ull;
-        iv = wave_upper_bound(A.n_excl, p16, lane, [&](uint64_t i) { return A.excl[2 * i + 1]; });
-        if (iv < A.n_excl) {
-            s_iv = uload64(A.excl + 2 * iv);
-            e_iv = uload64(A.excl + 2 * iv + 1);
-        }
+        const IvHit h = interval_after(A, p16, hint, lane);
+        iv = hint = h.iv;
+        const uint64_t s_iv = h.s, e_iv = h.e;
         uint32_t C, V, EN, ne, own;
         const ChunkMask m{glo, 0, 0};
         front_end<K, false>(d, A, p16, lane, m, iv, C, V, EN, ne, own);
         if (s_iv < c0 || t_n(own) < (uint32_t)(K - 1)) {   // an interval ends past p16 but starts before c0
-            warm<K>(A, lane);
+            warm_hinted<K>(A, lane, hint);
             return;
         }
         carry = own;
         ivs_r = iv < A.n_excl ? rel_of(s_iv) : 0xFFFFFFFFu;
         ive_r = iv < A.n_excl ? rel_of(e_iv) : 0xFFFFFFFFu;
         ivs_a = s_iv, ive_a = e_iv;
+    }
+    // warm with the interval search from `hint` (see warm16)
+    template <int K>
+    __device__ __forceinline__ void warm_hinted(const CountArgs& A, int lane, uint64_t& hint) {
+        carry = tail_pack(0, 0, 0);
+        for (int64_t p = (int64_t)c0; p > (int64_t)glo && !tail_complete<K>(carry);) {
+            p -= kChunk;
+            carry = tail_combine<K>(chunk_tail<K>(A.bytes, A.excl, A.n_excl, p, glo, lane), carry);
+        }
+        const IvHit h = interval_after(A, c0, hint, lane);
+        iv = hint = h.iv;
+        ivs_a = h.s, ive_a = h.e;
+        ivs_r = iv < A.n_excl ? rel_of(ivs_a) : 0xFFFFFFFFu;
+        ive_r = iv < A.n_excl ? rel_of(ive_a) : 0xFFFFFFFFu;
     }
     __device__ __forceinline__ void find_interval(const CountArgs& A, int lane) {
         // first excluded interval ending after c0; its bounds live in registers so
@@ -461,6 +513,32 @@ __device__ __forceinline__ uint32_t wave_frac(uint32_t w, uint32_t wts) {
 __device__ __forceinline__ uint64_t split_at_frac(uint64_t plo, uint64_t phi, uint32_t fr) {
     if (fr >= (1u << 20)) return phi;
     const uint64_t x = (plo + (((phi - plo) * fr) >> 20)) & ~(uint64_t)15;
+    return min(max(x, plo), phi);
+}
+
+// As split_at_frac with the interior points on the lattice base + kLattice m,
+// base = plo & ~15 (wave 0's c0) and kLattice the K1x wave iteration: every
+// wave range but the piece's last then ends on an iteration boundary of its own
+// walk (it starts at a lattice point too), so its last iteration is a whole one
+// and can take the fast path; only the first range (the genome's header, an
+// unaligned plo) and the last (the ragged end) need the general one.
+//   nit = lattice_iters(plo, phi), the iterations of [base, phi), once per piece
+// (phi - plo < 2^41; a division by a constant: a multiply); the point of
+// fraction fr is iteration round(nit fr), one multiply as in split_at_frac.
+// Rounding to nearest keeps a wave's share within half an iteration of its
+// weight, whatever the piece's length; a piece of fewer iterations than waves
+// leaves some ranges empty.  The same fr gives the same point: monotone, covering.
+constexpr uint32_t kLattice = 3 * kChunk;
+__device__ __forceinline__ uint32_t lattice_iters(uint64_t plo, uint64_t phi) {
+    return (uint32_t)((phi - (plo & ~(uint64_t)15) + (kLattice - 1)) >> 10) / (kLattice >> 10);
+}
+// lat = false: the point of split_at_frac (pieces too long for the lattice, see
+// kLatticeMaxIters), through the same single multiply.
+__device__ __forceinline__ uint64_t split_at_lattice(uint64_t plo, uint64_t phi, uint32_t nit, bool lat, uint32_t fr) {
+    if (fr == 0) return plo;
+    if (fr >= (1u << 20)) return phi;
+    const uint64_t m = ((lat ? (uint64_t)nit : phi - plo) * fr + (lat ? 1u << 19 : 0u)) >> 20;
+    const uint64_t x = lat ? (plo & ~(uint64_t)15) + m * kLattice : (plo + m) & ~(uint64_t)15;
     return min(max(x, plo), phi);
 }
 
