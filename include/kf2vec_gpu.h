@@ -273,6 +273,47 @@ int kf_sparse_count(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n_ge
                     void* d_work, uint64_t work_bytes, uint64_t* d_keys, uint32_t* d_counts,
                     uint64_t* d_nuniq, void* stream);
 
+/* ---- the get_kmers matrix (main.py:147-172) built on the device, from the keys
+ * and counts kf_sparse_count leaves there (or the non-zero bins of a
+ * kf_count_batch row, as standard codes): float32 rows of k + 1 columns, the k
+ * bases of a k-mer as get_kmers digits (A0 T1 C2 G3, main.py:118; first base
+ * first) and then its count divided by its genome's divisor.  One call writes
+ * the rows [row_lo, row_hi) (the SLAB) of a matrix that n_seg segments (genomes)
+ * tile, so a matrix of any size can be produced through a fixed buffer:
+ *   d_keys, d_counts : standard codes (A0 C1 G2 T3, first base most significant)
+ *                      and counts, u32 (count_bytes = 4) or u64 (8)
+ *   d_src0[n_seg]    : index in d_keys / d_counts of segment s's first k-mer
+ *   d_n[n_seg]       : the number of k-mers (rows) of segment s; the caller
+ *                      vouches that d_src0[s] + d_n[s] entries are readable
+ *   d_dst0[n_seg+1]  : the matrix row of segment s's first k-mer, non-decreasing;
+ *                      d_dst0[n_seg] is the number of matrix rows
+ *   d_denom[n_seg]   : segment s's divisor
+ *   d_out            : the slab, 16-byte aligned, (row_hi - row_lo) x (k + 1)
+ *                      floats, row-major; its element 0 is (row_lo, column 0)
+ * Matrix row d_dst0[s] + i (i < d_n[s]) holds the digits 0.0f .. 3.0f of key
+ * d_keys[d_src0[s] + i] and (float)count / d_denom[s]: conversion and division
+ * round to nearest even (IEEE), bit-equal to numpy's
+ * `c.astype(np.float32) / np.float32(denom)`.  Every other row -- those of
+ * [d_dst0[s] + d_n[s], d_dst0[s+1]) and those below d_dst0[0] -- is written as
+ * zeros.  So d_dst0 = the exclusive prefix sum of d_n gives the genomes' matrices
+ * packed back to back, and d_dst0[s] = s * Nmax a zero-padded [n_seg, Nmax, k+1]
+ * batch that needs no memset.  Every float of the slab is written once; nothing
+ * outside it is.  The tables are checked on the device: if d_dst0 decreases,
+ * d_n[s] > d_dst0[s+1] - d_dst0[s] or row_hi > d_dst0[n_seg], then *d_status = 2
+ * and nothing of d_out is written; otherwise *d_status = 0.  KF_EINVAL, before
+ * anything is launched, for k outside 2..31, count_bytes not 4 or 8, n_seg < 0,
+ * row_lo > row_hi, a null pointer or a misaligned one (8 bytes for the u64
+ * arrays, count_bytes for d_counts, 4 for d_denom and d_status, 16 for d_out).
+ * n_seg == 0 writes *d_status = 0 and nothing else; an empty slab (row_lo ==
+ * row_hi) checks the tables and writes no row.  One launch: asynchronous on
+ * `stream`, no allocation, no workgroup waits for another.  The kernel works in
+ * tiles of kf_kmers_tile_rows() slab rows (a multiple of 4). */
+int kf_kmers_tile_rows(void);
+int kf_kmers_rows(const uint64_t* d_keys, const void* d_counts, int count_bytes,
+                  const uint64_t* d_src0, const uint64_t* d_n, const uint64_t* d_dst0,
+                  const float* d_denom, int32_t n_seg, int k, uint64_t row_lo, uint64_t row_hi,
+                  float* d_out, uint32_t* d_status, void* stream);
+
 /* Hash of the sources this library was built from (csrc/ + this header, as
  * kf2vecfsw_amd/build.py computes it): 16 hex digits, with a "+<tag>" suffix for
  * profiling builds.  The Python binding refuses a library whose id differs from

@@ -62,6 +62,8 @@ SIGNATURES = {
     "kf_read_files":(_int, [ctypes.POINTER(_cp), _i32, _vp, _vp, _vp, _u64, _int]),
     "kf_sparse_workspace_bytes": (_u64, [_int, _u64, _i32]),
     "kf_sparse_count": (_int, [_vp, _vp, _i32, _u64, _vp, _u64, _int, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "kf_kmers_tile_rows": (_int, []),
+    "kf_kmers_rows": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _i32, _int, _u64, _u64, _vp, _vp, _vp]),
 }
 
 

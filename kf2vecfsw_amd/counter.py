@@ -508,16 +508,23 @@ class SparseCounter:
                 nuniq.data_ptr(), s), "kf_sparse_count")
         return keys, counts, nuniq[: db.n]
 
-    def to_host(self, keys: torch.Tensor, counts: torch.Tensor, nuniq: torch.Tensor,
-                off: np.ndarray) -> list[tuple[np.ndarray, np.ndarray]]:
-        """Per genome (keys uint64[m], counts uint32[m]) on the host: each genome's
-        slice is gathered on the device and the batch copied back once."""
+    @staticmethod
+    def nuniq_to_host(nuniq: torch.Tensor) -> np.ndarray:
+        """count()'s nuniq on the host (int64[n]); raises the library's error if
+        the device refused the offsets or its order check failed."""
         nu = nuniq.cpu().numpy()
         if nu.size and (nu == -1).any():   # UINT64_MAX: the library refused the offsets
             raise N.NativeError("kf_sparse_count: genome offsets must be non-decreasing and end at or below "
                                 "batch_bytes (nothing was counted)")
         if nu.size and (nu == -2).any():   # UINT64_MAX - 1: the device's order check failed
             raise N.NativeError("kf_sparse_count: the sorted keys failed the device's order check")
+        return nu
+
+    def to_host(self, keys: torch.Tensor, counts: torch.Tensor, nuniq: torch.Tensor,
+                off: np.ndarray) -> list[tuple[np.ndarray, np.ndarray]]:
+        """Per genome (keys uint64[m], counts uint32[m]) on the host: each genome's
+        slice is gathered on the device and the batch copied back once."""
+        nu = self.nuniq_to_host(nuniq)
         if nu.size == 0 or int(nu.sum()) == 0:
             return [(np.zeros(0, np.uint64), np.zeros(0, np.uint32)) for _ in range(nu.size)]
         idx = torch.cat([torch.arange(int(off[g]), int(off[g]) + int(nu[g]), device=keys.device)
@@ -560,6 +567,157 @@ def features(counts: torch.Tensor, pseudocount: bool = False, raw_cnt: bool = Fa
     if not raw_cnt:
         v = v / v.sum(dim=1, keepdim=True)
     return v * scaler if scaler != 1.0 else v
+
+
+# ---------------------------------------------------------------------------
+# the get_kmers matrix on the device (kf_kmers_rows)
+# ---------------------------------------------------------------------------
+def kmers_tile_rows() -> int:
+    """Slab rows per tile of the kf_kmers_rows kernel (a multiple of 4)."""
+    return int(N.lib().kf_kmers_tile_rows())
+
+
+@dataclasses.dataclass
+class KmersTables:
+    """kf_kmers_rows' segment tables on the device (one upload): segment s's
+    k-mers are keys[src0[s] : src0[s] + n[s]], its first matrix row dst0[s]."""
+    src0: torch.Tensor    # int64 [n_seg]
+    n: torch.Tensor       # int64 [n_seg]
+    dst0: torch.Tensor    # int64 [n_seg + 1]; dst0[n_seg] = the matrix's rows
+    denom: torch.Tensor   # float32 [n_seg]
+    n_seg: int
+    rows: int
+
+
+def kmers_tables(src0, n, dst0, denom, device: torch.device | str) -> KmersTables:
+    """Upload the tables of a kf_kmers_rows call (host arrays: src0[n_seg],
+    n[n_seg], dst0[n_seg + 1], denom[n_seg]) as one staged copy."""
+    ns = len(n)
+    dst0 = np.asarray(dst0, dtype=np.int64)
+    assert len(src0) == ns and len(denom) == ns and dst0.size == ns + 1
+    host = np.zeros(3 * ns + 1 + (ns + 1) // 2, dtype=np.int64)
+    host[:ns] = np.asarray(src0, dtype=np.int64)
+    host[ns: 2 * ns] = np.asarray(n, dtype=np.int64)
+    host[2 * ns: 3 * ns + 1] = dst0
+    host[3 * ns + 1:].view(np.float32)[:ns] = np.asarray(denom, dtype=np.float32)
+    t = torch.from_numpy(host)
+    if torch.cuda.is_available():
+        t = t.pin_memory()
+    t = t.to(torch.device(device), non_blocking=True)
+    return KmersTables(t[:ns], t[ns: 2 * ns], t[2 * ns: 3 * ns + 1], t[3 * ns + 1:].view(torch.float32)[:ns], ns,
+                       int(dst0[-1]))
+
+
+def kmers_rows(keys: torch.Tensor, counts: torch.Tensor, tab: KmersTables, k: int, row_lo: int, row_hi: int,
+               out: torch.Tensor, status: torch.Tensor, stream: int | None = None) -> None:
+    """Enqueue kf_kmers_rows on the current stream: the rows [row_lo, row_hi) of
+    the get_kmers matrix that `tab` lays out, float32 [row_hi - row_lo, k + 1],
+    into `out` (element 0 = row row_lo, column 0).  keys int64 holding uint64
+    standard codes; counts int32 holding uint32, or int64.  status (int32, one
+    word): 2 if the device refused the tables (nothing written), else 0 -- the
+    caller reads it back before it uses the rows."""
+    assert keys.dtype == torch.int64 and keys.is_contiguous() and counts.is_contiguous()
+    assert counts.dtype in (torch.int32, torch.int64)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= (row_hi - row_lo) * (k + 1)
+    assert status.dtype == torch.int32 and status.numel() >= 1
+    s = _stream_ptr(out.device) if stream is None else stream
+    with torch.cuda.device(out.device):
+        N.check(N.lib().kf_kmers_rows(keys.data_ptr(), counts.data_ptr(), 4 if counts.dtype == torch.int32 else 8,
+                                      tab.src0.data_ptr(), tab.n.data_ptr(), tab.dst0.data_ptr(),
+                                      tab.denom.data_ptr(), tab.n_seg, k, int(row_lo), int(row_hi), out.data_ptr(),
+                                      status.data_ptr(), s), "kf_kmers_rows")
+
+
+KMERS_EXACT_SUM = 1 << 24   # below this a float32 sum of whole numbers is exact in any order
+
+
+def kmers_denominators(counts: torch.Tensor, src0, n) -> np.ndarray:
+    """float32 [n_seg]: each segment's divisor of the get_kmers weights, equal
+    bit for bit to main.kmers_matrix's `np.sum(c.astype(np.float32))` over its
+    counts (counts int32 holding uint32 bit patterns, or int64; segment s is
+    counts[src0[s] : src0[s] + n[s]]).  The exact integer total is summed where
+    the counts are; below 2^24 every partial sum of the float32 counts is a whole
+    number float32 holds, so np.sum gives float32(total) in any order.  From 2^24
+    on np.sum's pairwise result depends on the rounding of its partial sums: that
+    segment's counts are copied back and summed by np.sum itself."""
+    u32 = counts.dtype == torch.int32
+    assert u32 or counts.dtype == torch.int64
+    seg = [counts[int(a): int(a) + int(m)] for a, m in zip(src0, n)]
+    if not seg:
+        return np.zeros(0, np.float32)
+    tot = torch.stack([c.sum(dtype=torch.int64) + (((c < 0).sum(dtype=torch.int64) << 32) if u32 else 0)
+                       for c in seg]).cpu().numpy()
+    den = tot.astype(np.float32)
+    for s in np.flatnonzero(tot >= KMERS_EXACT_SUM):
+        c = seg[s].cpu().numpy()
+        den[s] = np.sum((c.view(np.uint32) if u32 else c).astype(np.float32))
+    return den
+
+
+_std_codes: dict = {}       # k -> uint64 [nbins] on the host
+_DEV_STD_CODES: dict = {}   # (k, device index) -> the same as int64 on the device
+
+
+def vocab_std_codes(k: int) -> np.ndarray:
+    """uint64 [nbins]: column -> the standard 2-bit code (A0 C1 G2 T3, first base
+    most significant) of the vocab's k-mer for that column, from vocab_text(k).
+    Not col2rep: that is the class's minimum in kf-code order, which can be the
+    other strand.  The vocab is sorted, so ascending columns are ascending codes."""
+    if k not in _std_codes:
+        v = np.frombuffer(vocab_text(k), dtype=np.uint8).reshape(-1, k + 1)[:, :k]
+        lut = np.zeros(256, dtype=np.uint64)
+        for ch, d in zip(b"ACGT", range(4)):
+            lut[ch] = d
+        code = np.zeros(v.shape[0], dtype=np.uint64)
+        for i in range(k):
+            code = (code << np.uint64(2)) | lut[v[:, i]]
+        _std_codes[k] = code
+    return _std_codes[k]
+
+
+def dense_present(counts: torch.Tensor, k: int):
+    """The non-zero bins of a dense count matrix (int32 [B, nbins] holding uint32,
+    as KmerCounter.count gives) in the sparse counter's form: (keys int64, counts
+    int32, nuniq int64[B] on the host, off int64[B] on the host) with genome g's
+    k-mers at keys[off[g] : off[g] + nuniq[g]], packed, keys ascending."""
+    assert counts.dim() == 2 and counts.dtype == torch.int32 and counts.shape[1] == num_bins(k)
+    dev = counts.device
+    key = (k, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _DEV_STD_CODES:   # immutable: one upload per (k, device) and process
+        _DEV_STD_CODES[key] = torch.from_numpy(vocab_std_codes(k).view(np.int64)).to(dev)
+    nz = counts != 0
+    nu = nz.sum(dim=1).cpu().numpy().astype(np.int64)
+    off = np.concatenate([[0], np.cumsum(nu)[:-1]]).astype(np.int64) if nu.size else np.zeros(0, np.int64)
+    cols = nz.nonzero()[:, 1]   # row-major: ascending columns inside a row
+    return _DEV_STD_CODES[key][cols], counts[nz], nu, off
+
+
+def kmers_features(keys: torch.Tensor | None, counts: torch.Tensor, nuniq: torch.Tensor | None, off, k: int
+                   ) -> torch.Tensor:
+    """In-memory hand-off to the FSW trainer (the analogue of `features`): the
+    device float32 tensor [B, Nmax, k + 1] that
+    `train_model_set.pad_input([np.load(f) for f in files])` (train_model_set.py:92-94)
+    builds from get_kmers' `.npy` files of the same genomes, without the files.
+    Takes SparseCounter.count's (keys, counts, nuniq) with the batch's offsets
+    `off`, or -- with keys, nuniq and off None -- KmerCounter.count's dense
+    [B, nbins] count matrix (k <= 12).  A genome without k-mers is a row of
+    zeros (get_kmers writes no file for it)."""
+    if counts.dim() == 2:
+        keys, counts, nu, off = dense_present(counts, k)
+    else:
+        nu = SparseCounter.nuniq_to_host(nuniq)
+        off = np.asarray(off, dtype=np.uint64)[: nu.size].astype(np.int64)
+    dev = counts.device
+    B, nmax = int(nu.size), int(nu.max()) if nu.size else 0
+    out = torch.empty((B, nmax, k + 1), dtype=torch.float32, device=dev)
+    if B == 0 or nmax == 0:
+        return out
+    tab = kmers_tables(off, nu, np.arange(B + 1, dtype=np.int64) * nmax, kmers_denominators(counts, off, nu), dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    kmers_rows(keys, counts, tab, k, 0, B * nmax, out, status)
+    if int(status.item()) != 0:
+        raise N.NativeError("kf_kmers_rows: the device refused the segment tables")
+    return out
 
 
 def synth_ids(n: int, g0: int = 0, g_stride: int = 1) -> list[int]:

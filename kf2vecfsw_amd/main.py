@@ -915,17 +915,125 @@ def _merge_sorted_counts(parts: list) -> tuple:
     return u, out
 
 
+KMERS_SLAB_BYTES = 32 << 20       # get_kmers: the device slab and each of the two pinned buffers of the row stream
+DENSE_PRESENT_BINS = 1 << 28      # get_kmers k <= 12: count-matrix entries whose non-zero bins are taken at once
+
+
+class _KmersNpyWriter:
+    """get_kmers' `.npy` files made on the device (main.py:147-176): the matrices
+    of a batch's genomes, packed back to back, leave kf_kmers_rows in slabs of
+    KMERS_SLAB_BYTES; a slab is copied to one of two pinned buffers and written
+    to the files it covers while the device fills and copies the next one.  A
+    file is the v1.0 `.npy` header for (n, k + 1) '<f4' C-order followed by its
+    rows: the bytes np.save writes for the same array.  Many small genomes share
+    a slab; a large one takes many."""
+
+    def __init__(self, k: int, device, output_dir: str):
+        self.k, self.device, self.output_dir = k, device, output_dir
+        self.slab_rows = max(1, KMERS_SLAB_BYTES // (4 * (k + 1)))
+        self._bufs, self._cap = None, 0
+
+    def _buffers(self, rows: int):
+        """The device slab, the two pinned buffers, their status words and events,
+        for slabs of min(rows, slab_rows) rows: a batch of small matrices does not
+        pay for pinning whole slabs (the buffers grow at least 2x up to the slab)."""
+        import torch
+        cap = min(self.slab_rows, rows)
+        if self._bufs is None or self._cap < cap:
+            self._cap = min(self.slab_rows, max(cap, 2 * self._cap))
+            m = self._cap * (self.k + 1)
+            self._bufs = None
+            self._bufs = (torch.empty(m, dtype=torch.float32, device=self.device),
+                          [torch.empty(m, dtype=torch.float32, pin_memory=True) for _ in range(2)],
+                          torch.zeros(2, dtype=torch.int32, pin_memory=True),
+                          [torch.cuda.Event() for _ in range(2)])
+        return self._bufs
+
+    def write(self, names: list[str], keys, counts, src0, n) -> None:
+        """Genome j's k-mers are keys[src0[j] : src0[j] + n[j]] (ascending standard
+        codes, int64) with `counts` (int32 holding uint32, or int64), on the
+        device; src0 and n on the host.  Prints what main.py:147-176 prints."""
+        import torch
+        from .counter import kmers_denominators, kmers_rows, kmers_tables
+        k, w = self.k, self.k + 1
+        n = np.asarray(n, dtype=np.int64)
+        dst0 = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+        rows = int(dst0[-1])
+        g, f = 0, None
+
+        def emit(lo: int, hi: int, h) -> None:
+            """The slab rows [lo, hi) (h: its floats on the host) to their files,
+            and the lines of every genome that ends at or before hi."""
+            nonlocal g, f
+            while g < len(names):
+                a, b = int(dst0[g]), int(dst0[g + 1])
+                if a == b:
+                    print(f"--- Processing {names[g]} ---")
+                    print(f"Warning: No valid ATCG k-mers found in {names[g]}")
+                    g += 1
+                    continue
+                if a >= hi:
+                    return
+                path = os.path.join(self.output_dir, f"{names[g]}_k{k}.npy")
+                if f is None:
+                    print(f"--- Processing {names[g]} ---")
+                    f = open(path, "wb")
+                    np.lib.format.write_array_header_1_0(f, {"descr": "<f4", "fortran_order": False,
+                                                             "shape": (b - a, w)})
+                x0, x1 = max(a, lo), min(b, hi)
+                f.write(memoryview(h[(x0 - lo) * w: (x1 - lo) * w]))
+                if x1 < b:
+                    return
+                f.close()
+                f = None
+                print(f"Saved: {path} (Shape: {(b - a, w)})")
+                g += 1
+
+        try:
+            if rows:
+                dslab, pin, pstat, ev = self._buffers(rows)
+                S = self._cap
+                tab = kmers_tables(src0, n, dst0, kmers_denominators(counts, src0, n), self.device)
+                nslab = -(-rows // S)
+                status = torch.empty(nslab, dtype=torch.int32, device=self.device)
+                prev = None
+
+                def drain(lo, hi, b):
+                    ev[b].synchronize()
+                    if int(pstat[b]) != 0:
+                        raise N.NativeError("kf_kmers_rows: the device refused the segment tables")
+                    emit(lo, hi, pin[b].numpy())
+
+                for i in range(nslab):
+                    lo, hi, b = i * S, min(rows, (i + 1) * S), i & 1
+                    kmers_rows(keys, counts, tab, k, lo, hi, dslab, status[i: i + 1])
+                    pin[b][: (hi - lo) * w].copy_(dslab[: (hi - lo) * w], non_blocking=True)
+                    pstat[b: b + 1].copy_(status[i: i + 1], non_blocking=True)
+                    ev[b].record(torch.cuda.current_stream(self.device))
+                    if prev is not None:
+                        drain(*prev)   # the file write of slab i - 1 overlaps the kernel and copy of slab i
+                    prev = (lo, hi, b)
+                drain(*prev)
+            emit(rows, rows, None)   # genomes without k-mers at the end of the batch
+        finally:
+            if f is not None:
+                f.close()
+
+
 def get_kmers(args) -> None:
     """kf2vec/main.py:112-184 on the GPU (the *.fna of input_dir in batches).
     k <= 12: the dense counter's rows, non-zero bins kept; k = 13..31 (the rest
     of the reference's 2..31): the sparse counter (device radix sort of every
     window's canonical code, kf_sparse_count); a FASTA file above SPLIT_BYTES
     goes through it in pieces (fasta_pieces) whose sorted results are merged on
-    the device, so no file size is refused."""
+    the device, so no file size is refused.  The matrices are built on the
+    device from the keys and counts (kf_kmers_rows) and streamed into the .npy
+    files (_KmersNpyWriter); sparse_kmers_matrix / kmers_matrix above are the
+    host statement of what it writes."""
     import glob
 
     import torch
-    from .counter import KmerCounter, SparseCounter, counts_to_numpy, pack_files, pack_ranges, to_device
+    from .counter import KmerCounter, SparseCounter, dense_present, pack_files, to_device
 
     if not os.path.exists(args.output_dir):             # main.py:121-122
         os.makedirs(args.output_dir)
@@ -942,11 +1050,12 @@ def get_kmers(args) -> None:
     budget = int(batch_gb * (1 << 30))
     if sparse:   # ~21 (k <= 16) / ~29 device bytes per input byte with the outputs; 32-bit offsets
         budget = min(budget, 1 << 30)
-    # dense k <= 12: the whole count matrix comes back to the host, 4 x bins per
-    # genome whatever its size (33.6 MB at k=12): at most -batch_gb of it per batch
+    # dense k <= 12: the count matrix takes 4 x bins per genome whatever its size
+    # (33.6 MB at k=12): at most -batch_gb of it per batch
     cap = None if sparse else _count_cap(4 * counter.nbins, batch_gb)
+    writer = _KmersNpyWriter(args.k, device, args.output_dir)
     if sparse and any(os.path.getsize(p) > SPLIT_BYTES for p in fasta_files):
-        _get_kmers_pieces(args, fasta_files, counter, device, budget)
+        _get_kmers_pieces(args, fasta_files, counter, device, budget, writer)
         return
     for idx in _batches(fasta_files, budget, max_files=cap):
         paths = [fasta_files[i] for i in idx]
@@ -954,32 +1063,29 @@ def get_kmers(args) -> None:
         hb = pack_files(paths, names, threads=host_threads(10))   # the reference's `jellyfish count -t 10`
         if sparse:
             keys, cnts, nu = counter.count(to_device(hb, device), int(hb.off[-1]))
-            per = counter.to_host(keys, cnts, nu, hb.off)
+            nuh = SparseCounter.nuniq_to_host(nu)              # raises the library's error
+            writer.write(names, keys, cnts, hb.off[: hb.n].astype(np.int64), nuh)
             del keys, cnts, nu
         else:
             counts, _ = counter.count(to_device(hb, device))
-            c = counts_to_numpy(counts)
-        for j, base_name in enumerate(names):
-            print(f"--- Processing {base_name} ---")
-            m = sparse_kmers_matrix(per[j][0], per[j][1], args.k) if sparse else kmers_matrix(c[j], args.k)
-            if m.shape[0] == 0:
-                print(f"Warning: No valid ATCG k-mers found in {base_name}")
-                continue
-            output_path = os.path.join(args.output_dir, f"{base_name}_k{args.k}.npy")
-            np.save(output_path, m)
-            print(f"Saved: {output_path} (Shape: {m.shape})")
+            step = max(1, DENSE_PRESENT_BINS // counter.nbins)   # genomes whose non-zero bins are taken at once
+            for g0 in range(0, len(names), step):
+                keys, cnts, nuh, off = dense_present(counts[g0: g0 + step], args.k)
+                writer.write(names[g0: g0 + step], keys, cnts, off, nuh)
+            del counts
 
 
-def _get_kmers_pieces(args, fasta_files: list[str], counter, device, budget: int) -> None:
+def _get_kmers_pieces(args, fasta_files: list[str], counter, device, budget: int, writer) -> None:
     """get_kmers' sparse path with files above SPLIT_BYTES: every file as its
     fasta_pieces, the pieces in batches of at most `budget` bytes, a file's
     piece results kept on the device until its last piece is counted, then
-    merged (_merge_sorted_counts) and written as main.py:147-176 does."""
+    merged (_merge_sorted_counts) and written as main.py:147-176 does (the
+    merged int64 counts go to the row kernel as they are)."""
     import torch
     from .counter import pack_ranges, to_device
     units = []                                    # (file index, start, end)
     for fi, p in enumerate(fasta_files):
-        for a, e in fasta_pieces(p, args.k):
+        for a, e in fasta_pieces(p, args.k, SPLIT_BYTES):
             units.append((fi, a, e))
     last = {fi: j for j, (fi, _, _) in enumerate(units)}
     pending: dict = {}
@@ -989,9 +1095,7 @@ def _get_kmers_pieces(args, fasta_files: list[str], counter, device, budget: int
         hb = pack_ranges([(fasta_files[fi], a, e) for fi, a, e in batch], threads=host_threads(10))
         db = to_device(hb, device)
         keys, cnts, nu = counter.count(db, int(hb.off[-1]))
-        nuh = nu.cpu().numpy()
-        if nuh.size and ((nuh == -1).any() or (nuh == -2).any()):
-            counter.to_host(keys, cnts, nu, hb.off)   # raises the library's error
+        nuh = counter.nuniq_to_host(nu)               # raises the library's error
         for j, (fi, _, _) in enumerate(batch):
             lo, m = int(hb.off[j]), int(nuh[j])
             pending.setdefault(fi, []).append((keys[lo: lo + m].clone(), cnts[lo: lo + m].clone()))
@@ -1000,14 +1104,7 @@ def _get_kmers_pieces(args, fasta_files: list[str], counter, device, budget: int
     def finish(fi):
         k_, c_ = _merge_sorted_counts(pending.pop(fi))
         base_name = os.path.basename(fasta_files[fi]).replace(".fna", "")   # main.py:127
-        print(f"--- Processing {base_name} ---")
-        m = sparse_kmers_matrix(k_.cpu().numpy().view(np.uint64), c_.cpu().numpy(), args.k)
-        if m.shape[0] == 0:
-            print(f"Warning: No valid ATCG k-mers found in {base_name}")
-            return
-        output_path = os.path.join(args.output_dir, f"{base_name}_k{args.k}.npy")
-        np.save(output_path, m)
-        print(f"Saved: {output_path} (Shape: {m.shape})")
+        writer.write([base_name], k_, c_, [0], [k_.numel()])
 
     done = 0
     for j, u in enumerate(units):
