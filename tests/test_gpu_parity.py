@@ -413,15 +413,16 @@ def test_bucket_kernel_synth_batch_vs_oracle(torch_dev, oracle, k):
     assert int(totals.sum()) == int(counts.astype(np.uint64).sum())
 
 
-@pytest.mark.parametrize("k", [9, 10, 11])
+@pytest.mark.parametrize("k", [9, 10, 11, 12])
 def test_bucket_staggered_pieces_every_genome(torch_dev, oracle, k):
     """Several pieces per workgroup (1,100 genomes on a 256-workgroup grid), so
     that the staggered workgroups (phase 1 of piece i before phase 2 of piece
     i - 1, two record slots) alternate slots and the others do not: every
-    genome bit-exact vs the oracle."""
+    genome bit-exact vs the oracle.  k = 12: 300 genomes (33.5 MB per row), so
+    the first 44 workgroups get a second piece."""
     import torch
     from kf2vecfsw_amd import counter as C
-    n = 1100
+    n = 300 if k == 12 else 1100
     db = C.synth_device_batch(n, 24_000, seed0=77, n_period=5, device=torch_dev)
     cnt, tot = counter(k, torch_dev).count(db)
     torch.cuda.synchronize()
