@@ -201,25 +201,10 @@ __device__ __forceinline__ uint32_t n_pieces(uint64_t len) {
 
 // pstart[g] = sum of n_pieces over genomes < g; one workgroup.
 __global__ void __launch_bounds__(1024) piece_scan_kernel(const uint64_t* goff, int32_t n, uint32_t* pstart) {
-    __shared__ uint32_t sh[1024];
-    const int t = threadIdx.x;
-    uint32_t carry = 0;
-    for (int32_t base = 0; base < n; base += 1024) {
-        const int32_t i = base + t;
-        const uint32_t v = i < n ? n_pieces(goff[i + 1] - goff[i]) : 0u;
-        sh[t] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const uint32_t o = t >= d ? sh[t - d] : 0u;
-            __syncthreads();
-            sh[t] += o;
-            __syncthreads();
-        }
-        if (i < n) pstart[i] = carry + sh[t] - v;
-        carry += sh[1023];
-        __syncthreads();
-    }
-    if (t == 0) pstart[n] = carry;
+    const uint32_t all = scan_with_carry(
+        (uint32_t)n, [&](uint32_t i) { return n_pieces(goff[i + 1] - goff[i]); },
+        [&](uint32_t i, uint32_t p) { pstart[i] = p; });
+    if (threadIdx.x == 0) pstart[n] = all;
 }
 
 // Zero the count rows of genomes split into several pieces (their pieces add

@@ -19,19 +19,21 @@
 //   NOT skipped: awk runs before seqkit) is not N-class;
 //   every other byte is kept as is (lowercase, IUPAC, stray '>': the counter
 //   treats them as it treats them anywhere).
-// Three launches: per-block kept counts, one-workgroup block scan, scatter.
+// Three launches, the compaction of kf_compact.h: per-block kept counts, their
+// scan by one workgroup (with carry over rounds of 1,024 blocks), scatter.
 // Record r's processed sequence is out[out_se[2r], out_se[2r+1]).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kf_compact.h"
 #include "kf_internal.h"
 
 namespace kf {
 namespace {
 
-constexpr int kCBlock = 256;                 // threads per workgroup
-constexpr int kCPer = 16;                    // bytes per thread
-constexpr uint32_t kCSpan = kCBlock * kCPer; // bytes per workgroup (4 KiB)
+constexpr int kCBlock = kCompactBlock;      // threads per workgroup
+constexpr int kCPer = kCompactPer;          // bytes per thread
+constexpr uint32_t kCSpan = kCompactSpan;   // bytes per workgroup (4 KiB)
 
 __device__ __forceinline__ bool is_n(uint8_t c) { return c == 'N' || c == 'n' || c == '|'; }
 __device__ __forceinline__ bool is_gap(uint8_t c) { return c == '-' || c == ' ' || c == '\t' || c == '.'; }
@@ -101,59 +103,17 @@ __device__ __forceinline__ uint32_t thread_keep(const uint8_t* bytes, uint64_t l
 
 __global__ void __launch_bounds__(kCBlock) chunk_count_kernel(const uint8_t* bytes, uint64_t len, const uint64_t* se,
                                                                 int32_t n, uint32_t* blk) {
-    __shared__ uint32_t red[kCBlock / 64];
-    const uint64_t p0 = (uint64_t)blockIdx.x * kCSpan + (uint64_t)threadIdx.x * kCPer;
     uint8_t ch[kCPer];
     uint32_t mask;
-    uint32_t c = thread_keep(bytes, len, se, n, p0, ch, mask);
-    for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// Exclusive scan of nb block counts in place (one workgroup), blk[nb] = total.
-__global__ void __launch_bounds__(1024) chunk_scan_kernel(uint32_t* blk, uint32_t nb) {
-    __shared__ uint32_t sh[1024];
-    const uint32_t t = threadIdx.x;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += 1024) {
-        const uint32_t i = base + t;
-        const uint32_t v = i < nb ? blk[i] : 0u;
-        sh[t] = v;
-        __syncthreads();
-        for (uint32_t d = 1; d < 1024; d <<= 1) {
-            const uint32_t o = t >= d ? sh[t - d] : 0u;
-            __syncthreads();
-            sh[t] += o;
-            __syncthreads();
-        }
-        if (i < nb) blk[i] = carry + sh[t] - v;
-        carry += sh[1023];
-        __syncthreads();
-    }
-    if (t == 0) blk[nb] = carry;
+    compact_count(thread_keep(bytes, len, se, n, compact_p0(), ch, mask), blk);
 }
 
 __global__ void __launch_bounds__(kCBlock) chunk_scatter_kernel(const uint8_t* bytes, uint64_t len, const uint64_t* se,
                                                                   int32_t n, const uint32_t* blk, uint8_t* out) {
-    __shared__ uint32_t wsum[kCBlock / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint64_t p0 = (uint64_t)blockIdx.x * kCSpan + (uint64_t)threadIdx.x * kCPer;
     uint8_t ch[kCPer];
     uint32_t mask;
-    const uint32_t c = thread_keep(bytes, len, se, n, p0, ch, mask);
-    // exclusive prefix of c over the workgroup
-    uint32_t inc = c;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int x = 0; x < w; ++x) before += wsum[x];
-    uint64_t pos = (uint64_t)blk[blockIdx.x] + before + inc - c;
+    const uint32_t c = thread_keep(bytes, len, se, n, compact_p0(), ch, mask);
+    uint64_t pos = compact_first_slot(blk[blockIdx.x], c);
     for (int q = 0; q < kCPer; ++q)
         if (mask & (1u << q)) out[pos++] = ch[q];
 }
@@ -208,7 +168,8 @@ extern "C" int kf_chunk_compact(const uint8_t* d_bytes, uint64_t len, const uint
     if (nb) {
         hipLaunchKernelGGL(chunk_count_kernel, dim3((uint32_t)nb), dim3(kCBlock), 0, s, d_bytes, len, d_seq, n_rec,
                            d_scratch);
-        hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(1024), 0, s, d_scratch, (uint32_t)nb);
+        hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, s, d_scratch, (uint32_t)nb,
+                           (uint64_t*)nullptr);
         hipLaunchKernelGGL(chunk_scatter_kernel, dim3((uint32_t)nb), dim3(kCBlock), 0, s, d_bytes, len, d_seq, n_rec,
                            d_scratch, d_out);
     } else {

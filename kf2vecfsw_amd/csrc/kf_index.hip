@@ -5,9 +5,10 @@
 // A header is a line that starts with '>' (at a genome start or after '\n'); it
 // is excluded up to its '\n' (or the genome end).  Unlike the host index, header
 // lines that follow each other stay separate pairs (the count kernels treat
-// adjacent ranges like one).  Three launches: per-block header counts, a
-// one-workgroup block scan, and a scatter of the pairs in order; the number of
-// pairs stays on the device (kf_count_batch_dev reads it there).
+// adjacent ranges like one).  Three launches, the compaction of kf_compact.h:
+// per-block header counts, their scan by one workgroup (with carry over rounds of
+// 1,024 blocks), and a scatter of the pairs in order; the number of pairs stays on
+// the device (kf_count_batch_dev reads it there).
 //
 // The FASTQ index (kf_index_fastq, second half of this file) covers genomes in
 // the regular four-line form, where a line's role is its number mod 4 and the
@@ -18,26 +19,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kf_compact.h"
 #include "kf_internal.h"
-#include "kf_scan.h"
 
 namespace kf {
 namespace {
 
-constexpr int kIBlock = 256;                   // threads per workgroup
-constexpr int kIPer = 16;                      // bytes per thread
-constexpr uint32_t kISpan = kIBlock * kIPer;   // 4 KiB per workgroup
-
-// genome of byte i (< goff[n]): the last g with goff[g] <= i
-__device__ __forceinline__ int genome_of(const uint64_t* goff, int n, uint64_t i) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int m = (lo + hi) >> 1;
-        if (goff[m] <= i) lo = m;
-        else hi = m;
-    }
-    return lo;
-}
+constexpr int kIBlock = kCompactBlock;     // threads per workgroup (also of the per-genome and per-pair kernels)
+constexpr int kIPer = kCompactPer;         // bytes per thread
+constexpr uint32_t kISpan = kCompactSpan;  // 4 KiB per workgroup
 
 // header starts among the thread's 16 bytes (bit q: byte p0 + q)
 __device__ __forceinline__ uint32_t thread_heads(const uint8_t* bytes, uint64_t end, const uint64_t* goff, int n,
@@ -52,8 +42,7 @@ __device__ __forceinline__ uint32_t thread_heads(const uint8_t* bytes, uint64_t 
         if (c == '>') {
             bool start = prev == '\n' || i == 0;
             if (!start) {   // a genome start (genomes need not end with '\n')
-                const int g = genome_of(goff, n, i);
-                start = goff[g] == i;
+                start = goff[last_at_or_before(n, i, [&](int g) { return goff[g]; })] == i;
             }
             if (start) m |= 1u << q;
         }
@@ -64,66 +53,21 @@ __device__ __forceinline__ uint32_t thread_heads(const uint8_t* bytes, uint64_t 
 
 __global__ void __launch_bounds__(kIBlock) idx_count_kernel(const uint8_t* bytes, uint64_t end, const uint64_t* goff,
                                                             int n, uint32_t* blk) {
-    __shared__ uint32_t red[kIBlock / 64];
-    const uint64_t p0 = (uint64_t)blockIdx.x * kISpan + (uint64_t)threadIdx.x * kIPer;
-    uint32_t c = (uint32_t)__builtin_popcount(thread_heads(bytes, end, goff, n, p0));
-    for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// exclusive scan of nb block counts in place (one workgroup); blk[nb] = total,
-// also written to *n_pairs
-__global__ void __launch_bounds__(1024) idx_scan_kernel(uint32_t* blk, uint32_t nb, uint64_t* n_pairs) {
-    __shared__ uint32_t sh[1024];
-    const uint32_t t = threadIdx.x;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += 1024) {
-        const uint32_t i = base + t;
-        const uint32_t v = i < nb ? blk[i] : 0u;
-        sh[t] = v;
-        __syncthreads();
-        for (uint32_t d = 1; d < 1024; d <<= 1) {
-            const uint32_t o = t >= d ? sh[t - d] : 0u;
-            __syncthreads();
-            sh[t] += o;
-            __syncthreads();
-        }
-        if (i < nb) blk[i] = carry + sh[t] - v;
-        carry += sh[1023];
-        __syncthreads();
-    }
-    if (t == 0) {
-        blk[nb] = carry;
-        *n_pairs = carry;
-    }
+    compact_count((uint32_t)__builtin_popcount(thread_heads(bytes, end, goff, n, compact_p0())), blk);
 }
 
 __global__ void __launch_bounds__(kIBlock) idx_scatter_kernel(const uint8_t* bytes, uint64_t end, const uint64_t* goff,
                                                               int n, const uint32_t* blk, uint64_t* excl,
                                                               uint64_t cap) {
-    __shared__ uint32_t wsum[kIBlock / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint64_t p0 = (uint64_t)blockIdx.x * kISpan + (uint64_t)threadIdx.x * kIPer;
+    const uint64_t p0 = compact_p0();
     uint32_t m = thread_heads(bytes, end, goff, n, p0);
-    const uint32_t c = (uint32_t)__builtin_popcount(m);
-    uint32_t inc = c;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int x = 0; x < w; ++x) before += wsum[x];
-    uint64_t u = (uint64_t)blk[blockIdx.x] + before + inc - c;
+    uint64_t u = compact_first_slot(blk[blockIdx.x], (uint32_t)__builtin_popcount(m));
     while (m) {
         const int q = __builtin_ctz(m);
         m &= m - 1;
         const uint64_t j = p0 + (uint64_t)q;
         if (u < cap) {
-            const uint64_t ge = goff[genome_of(goff, n, j) + 1];
+            const uint64_t ge = goff[last_at_or_before(n, j, [&](int g) { return goff[g]; }) + 1];   // its genome's end
             uint64_t e = j;
             while (e < ge && bytes[e] != '\n') ++e;   // the header line (short)
             excl[2 * u] = j;
@@ -188,32 +132,18 @@ __device__ __forceinline__ uint32_t thread_newlines(const uint8_t* bytes, uint64
 }
 
 __global__ void __launch_bounds__(kIBlock) fq_count_kernel(const uint8_t* bytes, uint64_t end, uint64_t* blk) {
-    __shared__ uint32_t red[kIBlock / 64];
-    const uint64_t p0 = (uint64_t)blockIdx.x * kISpan + (uint64_t)threadIdx.x * kIPer;
-    uint32_t c = (uint32_t)__builtin_popcount(thread_newlines(bytes, end, p0));
-    for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    compact_count((uint32_t)__builtin_popcount(thread_newlines(bytes, end, compact_p0())), blk);
 }
 
 // One scan level: workgroup i replaces v[i * 1024 + t] (entries below n) by their
 // exclusive prefix sums and writes their total to sums[i].
 __global__ void __launch_bounds__(kQLevel) fq_scan_level_kernel(uint64_t* v, uint64_t n, uint64_t* sums) {
-    __shared__ uint64_t sh[kQLevel];
-    const uint32_t t = threadIdx.x;
-    const uint64_t i = (uint64_t)blockIdx.x * kQLevel + t;
-    const uint64_t x = i < n ? v[i] : 0;
-    sh[t] = x;
-    __syncthreads();
-    for (uint32_t d = 1; d < kQLevel; d <<= 1) {
-        const uint64_t o = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += o;
-        __syncthreads();
-    }
-    if (i < n) v[i] = sh[t] - x;
-    if (t == kQLevel - 1) sums[blockIdx.x] = sh[t];
+    __shared__ uint64_t wsum[kQLevel / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kQLevel + threadIdx.x;
+    uint64_t all;
+    const uint64_t ex = block_excl_scan<kQLevel / 64>(i < n ? v[i] : (uint64_t)0, wsum, &all);
+    if (i < n) v[i] = ex;
+    if (threadIdx.x == 0) sums[blockIdx.x] = all;
 }
 
 // entry i of a scanned table: its three levels added up
@@ -224,17 +154,9 @@ __device__ __forceinline__ uint64_t scanned(const uint64_t* v, const uint64_t* s
 __global__ void __launch_bounds__(kIBlock) fq_scatter_kernel(const uint8_t* bytes, uint64_t end, const uint64_t* blk,
                                                              const uint64_t* blk1, const uint64_t* blk2,
                                                              uint64_t* nlpos, uint64_t cap_lines) {
-    __shared__ uint32_t wsum[kIBlock / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint64_t p0 = (uint64_t)blockIdx.x * kISpan + (uint64_t)threadIdx.x * kIPer;
+    const uint64_t p0 = compact_p0();
     uint32_t m = thread_newlines(bytes, end, p0);
-    const uint32_t c = (uint32_t)__builtin_popcount(m);
-    const uint32_t inc = wave_incl_scan(c);   // every thread of the workgroup is here
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int x = 0; x < w; ++x) before += wsum[x];
-    uint64_t u = scanned(blk, blk1, blk2, blockIdx.x) + before + inc - c;
+    uint64_t u = compact_first_slot(scanned(blk, blk1, blk2, blockIdx.x), (uint32_t)__builtin_popcount(m));
     while (m) {
         const int q = __builtin_ctz(m);
         m &= m - 1;
@@ -301,13 +223,10 @@ __global__ void __launch_bounds__(kIBlock) fq_pair_kernel(const uint8_t* bytes, 
                                                           uint64_t* excl, uint64_t cap_pairs, uint32_t* status) {
     const uint64_t q = (uint64_t)blockIdx.x * kIBlock + threadIdx.x;
     if (q >= cap_pairs || q >= *n_pairs || *n_lines > cap_lines) return;
-    int lo = 0, hi = n;   // the last genome whose first pair is at or before q
-    while (hi - lo > 1) {
-        const int m = (lo + hi) >> 1;
-        if (scanned(g_pairs, g_pairs1, g_pairs2, (uint64_t)m) <= q) lo = m;
-        else hi = m;
-    }
-    const uint64_t g = (uint64_t)lo, r = q - scanned(g_pairs, g_pairs1, g_pairs2, g);
+    // the last genome whose first pair is at or before q
+    const uint64_t g = (uint64_t)last_at_or_before(
+        n, q, [&](int m) { return scanned(g_pairs, g_pairs1, g_pairs2, (uint64_t)m); });
+    const uint64_t r = q - scanned(g_pairs, g_pairs1, g_pairs2, g);
     const uint64_t lines = g_lines[g], a = goff[g], cend = g_end[g];
     const uint64_t* nl = nlpos + g_nl[g];   // nl[j]: the '\n' that ends line j (j < lines - 1)
     if (lines == 0 || r >= 1 + (lines + 1) / 4) return;   // cannot happen: q is one of this genome's pairs
@@ -370,7 +289,7 @@ extern "C" int kf_index_fasta(const uint8_t* d_bytes, const uint64_t* d_goff, in
         return kf_fail(KF_ERANGE, "scratch needs %llu words", (unsigned long long)(nb + 1));
     hipLaunchKernelGGL(idx_count_kernel, dim3((uint32_t)nb), dim3(kIBlock), 0, s, d_bytes, batch_bytes, d_goff,
                        n_genomes, d_scratch);
-    hipLaunchKernelGGL(idx_scan_kernel, dim3(1), dim3(1024), 0, s, d_scratch, (uint32_t)nb, d_n_pairs);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, s, d_scratch, (uint32_t)nb, d_n_pairs);
     hipLaunchKernelGGL(idx_scatter_kernel, dim3((uint32_t)nb), dim3(kIBlock), 0, s, d_bytes, batch_bytes, d_goff,
                        n_genomes, d_scratch, d_excl, cap_pairs);
     if (hipGetLastError() != hipSuccess) return kf_fail(KF_EHIP, "record index launch failed");

@@ -1,5 +1,15 @@
 // kf_scan.h -- LDS and wave prefix-sum helpers shared by the device sources (also
-// by kf_sparse.hip, which does not use the count front end, kf_front.h).
+// by kf_sparse.hip, which does not use the count front end, kf_front.h): the wave
+// and workgroup scans, the one-workgroup scan with carry of the device pre-passes
+// and the per-thread search of a sorted table (kf_compact.h builds the pre-passes'
+// count -> scan -> scatter compaction on them).
+//
+// Every workgroup helper (block_excl_scan, block_sum, scan_with_carry, and
+// kf_compact.h's compact_count and compact_first_slot) must be reached by EVERY
+// thread of a workgroup of whole waves: the DPP wave scan reads its neighbours'
+// lanes and the barriers wait for every wave.  A thread with nothing to add brings
+// 0 (the pre-passes' predicates return 0 past the end of the input); it does not
+// leave the kernel first.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +44,82 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31
     return v;
+}
+// 64-bit values: __shfl_up steps on the whole value (ds_bpermute; the FASTQ
+// index's scan levels only, which are not hot).
+__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v) {
+    const int lane = threadIdx.x & 63;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_up((unsigned long long)v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// Exclusive prefix of one value per thread over an NW-wave workgroup; *total
+// (optional) gets the sum.  wsum: NW words of LDS.  Contains two barriers
+// (LDS-only ones if LDSB), the second after the last read of wsum.
+template <int NW, bool LDSB = false, typename T>
+__device__ __forceinline__ T block_excl_scan(T v, T* wsum, T* total = nullptr) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const T inc = wave_incl_scan(v);
+    if (lane == 63) wsum[w] = inc;
+    if (LDSB) lds_barrier();
+    else __syncthreads();
+    T before = 0, all = 0;
+#pragma unroll
+    for (int x = 0; x < NW; ++x) {
+        const T s = wsum[x];
+        before += x < w ? s : T(0);
+        all += s;
+    }
+    if (total) *total = all;
+    if (LDSB) lds_barrier();
+    else __syncthreads();
+    return before + inc - v;
+}
+
+// Sum of one value per thread over an NW-wave workgroup, to every thread.  red:
+// NW words of LDS.  One barrier, after the writes of red.
+template <int NW>
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* red) {
+    const uint32_t inc = wave_incl_scan(v);
+    if ((threadIdx.x & 63) == 63) red[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    uint32_t all = 0;
+#pragma unroll
+    for (int x = 0; x < NW; ++x) all += red[x];
+    return all;
+}
+
+// Exclusive scan of load(0) .. load(n - 1) by ONE workgroup of 1,024 threads,
+// 1,024 entries per round with the rounds' carry in a register: store(i, prefix)
+// for every i < n, in place if load and store name the same table (entry i is read
+// and written by one thread).  Returns the total to every thread.
+template <typename Load, typename Store>
+__device__ __forceinline__ uint32_t scan_with_carry(uint32_t n, Load load, Store store) {
+    __shared__ uint32_t wsum[16];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n; base += 1024) {
+        const uint32_t i = base + threadIdx.x;
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan<16>(i < n ? (uint32_t)load(i) : 0u, wsum, &tot);
+        if (i < n) store(i, carry + ex);
+        carry += tot;
+    }
+    return carry;
+}
+
+// The last g in [0, n) with key(g) <= x, or 0 if there is none (key ascending).
+template <typename X, typename Key>
+__device__ __forceinline__ int last_at_or_before(int n, X x, Key key) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int m = (lo + hi) >> 1;
+        if (key(m) <= x) lo = m;
+        else hi = m;
+    }
+    return lo;
 }
 
 }  // namespace kf

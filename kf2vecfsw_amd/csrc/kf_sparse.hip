@@ -122,18 +122,6 @@ __device__ __forceinline__ uint32_t sp_code(uint8_t c) {
     return base ? (x ^ (x >> 1)) : (c == '\n' ? 4u : 5u);
 }
 
-// Segment of tile t (t < tfirst[n]): the last g with tfirst[g] <= t (empty
-// segments share their tfirst with the next one).
-__device__ __forceinline__ int tile_genome(const uint32_t* tfirst, int n, uint32_t t) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int m = (lo + hi) >> 1;
-        if (tfirst[m] <= t) lo = m;
-        else hi = m;
-    }
-    return lo;
-}
-
 struct TileSpan {
     uint32_t g, gs, ge, base, cnt;   // segment, its slot range, the tile's first slot and slot count
 };
@@ -151,35 +139,12 @@ __device__ __forceinline__ bool tile_span(const uint64_t* goff, const uint32_t* 
     return true;
 }
 
-// Exclusive prefix of one value per thread over an NW-wave workgroup; *total
-// (optional) gets the sum.  Contains two barriers (LDS-only ones if LDSB).
-template <int NW, bool LDSB = false>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total = nullptr) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t inc = wave_incl_scan(v);
-    if (lane == 63) wsum[w] = inc;
-    if (LDSB) lds_barrier();
-    else __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int x = 0; x < NW; ++x) {
-        const uint32_t s = wsum[x];
-        before += x < w ? s : 0u;
-        all += s;
-    }
-    if (total) *total = all;
-    if (LDSB) lds_barrier();
-    else __syncthreads();
-    return before + inc - v;
-}
-
 // ---- tiles: tfirst[g] = exclusive prefix of ceil(len_g / span), tfirst[n] = total.
 // A goff that decreases or ends past batch_bytes (the buffers' size) sets
 // tfirst[n+1] and leaves every tile count at 0: nothing is read or written, and
 // every genome's distinct-k-mer count comes back as UINT64_MAX.
 __global__ void __launch_bounds__(1024) sp_tiles_kernel(const uint64_t* goff, int n, uint64_t batch_bytes,
                                                         uint32_t span, uint32_t* tfirst) {
-    __shared__ uint32_t sh[1024];
     __shared__ int bad;
     const int t = threadIdx.x;
     if (t == 0) bad = goff[n] > batch_bytes;
@@ -188,24 +153,11 @@ __global__ void __launch_bounds__(1024) sp_tiles_kernel(const uint64_t* goff, in
         if (goff[g + 1] < goff[g]) bad = 1;
     __syncthreads();
     const bool ok = !bad;
-    uint32_t carry = 0;
-    for (int base = 0; base < n; base += 1024) {
-        const int g = base + t;
-        const uint32_t v = g < n && ok ? (uint32_t)((goff[g + 1] - goff[g] + span - 1) / span) : 0u;
-        sh[t] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const uint32_t o = t >= d ? sh[t - d] : 0u;
-            __syncthreads();
-            sh[t] += o;
-            __syncthreads();
-        }
-        if (g < n) tfirst[g] = carry + sh[t] - v;
-        carry += sh[1023];
-        __syncthreads();
-    }
+    const uint32_t all = scan_with_carry(
+        (uint32_t)n, [&](uint32_t g) { return ok ? (uint32_t)((goff[g + 1] - goff[g] + span - 1) / span) : 0u; },
+        [&](uint32_t g, uint32_t p) { tfirst[g] = p; });
     if (t == 0) {
-        tfirst[n] = carry;
+        tfirst[n] = all;
         tfirst[n + 1] = ok ? 0u : 1u;
     }
 }
@@ -221,7 +173,8 @@ __global__ void __launch_bounds__(256) sp_tilemap_kernel(const uint64_t* goff, u
         xlo[t] = n_excl;
         return;
     }
-    const int g = tile_genome(tfirst, n, t);
+    // the last g with tfirst[g] <= t (empty segments share their tfirst with the next one)
+    const int g = last_at_or_before(n, t, [&](int m) { return tfirst[m]; });
     tfirst[n + 2 + t] = (uint32_t)g;
     const uint64_t base = goff[g] + (uint64_t)(t - tfirst[g]) * span;
     uint32_t lo = 0, h = n_excl;

@@ -2,8 +2,9 @@
 bucket_kernel<K> in csrc/kf_bucket.hip): rounds whose windows all fall into one
 bucket, pieces at the size limit kPieceMax, the phase-2 round shares of the 16
 waves (rw0 / rw1) over a lattice of round counts, piece and wave boundaries
-(split_at) placed against headers, N runs and newline runs, and a count after
-kf_workspace_release.  Every count row and total is compared bit for bit
+(split_at) placed against headers, N runs and newline runs, a count after
+kf_workspace_release, and a piece table of more than 2,048 genomes (three rounds
+of piece_scan_kernel).  Every count row and total is compared bit for bit
 against the CPU oracle, as in test_gpu_parity.py.  Run on an MI355X:
 `pytest -m gpu`."""
 import numpy as np
@@ -304,3 +305,44 @@ def test_count_after_workspace_release(torch_dev, oracle, native):
     check(oracle, blobs, 11, counts, totals, tag="after-release-k11")
     forget(blobs, 10)
     forget(blobs, 11)
+
+
+# ------------------------------------------ 6. piece table past two scan rounds
+PIECE_TABLE_GENOMES = 2050
+PIECE_TABLE_ROWS = (0, 1022, 1023, 1024, 2046, 2047, 2048, 2049)   # around the rounds' ends (1,024 genomes each)
+
+
+def test_piece_table_third_scan_round(torch_dev, oracle, native):
+    """2,050 genomes at k = 10: piece_scan_kernel scans the pieces per genome in
+    rounds of 1,024 and carries the sum over, so genomes 2,048 and 2,049 take
+    their first piece from the carry of two rounds.  Genomes of 0 to 300 bases,
+    two in three with a header, at unaligned offsets; genomes 1,023 and 2,047
+    (the last of a round) are empty and still own a piece.  On the device:
+    every row's sum equals its total, and both the oracle's total.  The rows
+    around the rounds' ends bit for bit; the count matrix (4.3 GB) stays on the
+    device."""
+    import torch
+    from kf2vecfsw_amd import counter as C
+    k, n = 10, PIECE_TABLE_GENOMES
+    rng = np.random.default_rng(2050)
+    blobs = [(b">g%d\n" % i if i % 3 else b"") + gen.wrap(gen.random_seq(rng, int(rng.integers(0, 301))),
+                                                          (None, 60, 80)[i % 3]) for i in range(n)]
+    gaps = rng.integers(0, 41, size=n)
+    for i in (1023, 2047):
+        blobs[i], gaps[i] = b"", 0
+    db = device_batch(blobs, gaps, torch_dev)
+    off = db.off.cpu().numpy()
+    assert db.n == n and off[1023] == off[1024] and off[2047] == off[2048]
+    want = np.asarray([oracle.count(b, k)[1] for b in blobs], np.int64)
+    assert want[1023] == 0 and want[2047] == 0 and want[2048] > 0 and want[2049] > 0 and (want[:2048] > 0).sum() > 1500
+    try:
+        cnt, tot = counter(k, torch_dev).count(db)
+        sums = cnt.sum(dim=1, dtype=torch.int64)
+        torch.cuda.synchronize()
+        bad = torch.nonzero((sums != tot) | (tot != torch.from_numpy(want).to(torch_dev))).flatten()[:5].tolist()
+        assert not bad, [(i, int(sums[i]), int(tot[i]), int(want[i])) for i in bad]
+        for i in PIECE_TABLE_ROWS:
+            assert (C.counts_to_numpy(cnt[i]) == oracle.count(blobs[i], k)[0]).all(), i
+    finally:
+        cnt = sums = None
+        assert native.kf_workspace_release() == 0
