@@ -314,6 +314,44 @@ int kf_kmers_rows(const uint64_t* d_keys, const void* d_counts, int count_bytes,
                   const float* d_denom, int32_t n_seg, int k, uint64_t row_lo, uint64_t row_hi,
                   float* d_out, uint32_t* d_status, void* stream);
 
+/* ---- the union of two sorted (key, count) lists on the device: how get_kmers
+ * joins the pieces of a FASTA file above 1 GiB (each piece's kf_sparse_count
+ * result into the file's running result), with two inputs and one output in
+ * memory and no sort.
+ *   d_keys_a[n_a], d_keys_b[n_b] : u64 keys, each list STRICTLY ASCENDING in
+ *                      unsigned order (what kf_sparse_count leaves per genome)
+ *   d_counts_a, d_counts_b : their counts, u32 (count_bytes = 4) or u64 (8),
+ *                      chosen per side; n_a and n_b are host values and may be 0
+ *   d_keys_out, d_counts_out : n_a + n_b u64 entries each; no overlap with an input
+ *   d_n_out          : one u64 on the device, the number of output entries
+ * The output is the ascending union of the keys: a key of both lists appears
+ * once with the sum of its two counts, a key of one list keeps its count, all
+ * counts as u64 (sums are not checked for wrap, like kf_rows_accumulate's
+ * totals).  Entries at and past *d_n_out are unspecified; nothing outside
+ * [0, n_a + n_b) of either output array is written.
+ * The order is checked on the device before anything depends on it: if either
+ * list has an adjacent pair that is equal or descending (anywhere: inside a tile
+ * of the kernel or across a tile edge), then *d_status = 1, *d_n_out = 0 and the
+ * merge kernels return without reading the lists; otherwise *d_status = 0.  For
+ * any input contents the call reads and writes only inside the stated arrays.
+ * KF_EINVAL, before anything is launched, for count_bytes not 4 or 8, n_a + n_b
+ * above 2^34 entries (the limit: one workgroup per tile within 2^32 threads per
+ * launch; index arithmetic is 64-bit throughout), a null pointer (the key and
+ * count pointers of a list of length 0 may be null) or a misaligned one (8 bytes
+ * for the u64 arrays, d_n_out and d_scratch, count_bytes for the counts, 4 for
+ * d_status).  KF_ERANGE if scratch_bytes < kf_sparse_merge_scratch_bytes(n_a,
+ * n_b) (16 B per tile and a few words; 0 for sizes above the limit).
+ * Merge path in tiles of kf_sparse_merge_tile() merged positions (a multiple of
+ * 64), one workgroup each: an order check, a count launch, the scan of the
+ * tiles' counts, a scatter launch.  Asynchronous on `stream`, no allocation, no
+ * host synchronisation, and no workgroup waits for another. */
+int      kf_sparse_merge_tile(void);
+uint64_t kf_sparse_merge_scratch_bytes(uint64_t n_a, uint64_t n_b);
+int kf_sparse_merge(const uint64_t* d_keys_a, const void* d_counts_a, int count_bytes_a, uint64_t n_a,
+                    const uint64_t* d_keys_b, const void* d_counts_b, int count_bytes_b, uint64_t n_b,
+                    uint64_t* d_keys_out, uint64_t* d_counts_out, uint64_t* d_n_out,
+                    uint32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* Hash of the sources this library was built from (csrc/ + this header, as
  * kf2vecfsw_amd/build.py computes it): 16 hex digits, with a "+<tag>" suffix for
  * profiling builds.  The Python binding refuses a library whose id differs from

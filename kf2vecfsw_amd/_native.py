@@ -64,6 +64,9 @@ SIGNATURES = {
     "kf_sparse_count": (_int, [_vp, _vp, _i32, _u64, _vp, _u64, _int, _vp, _u64, _vp, _vp, _vp, _vp]),
     "kf_kmers_tile_rows": (_int, []),
     "kf_kmers_rows": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _i32, _int, _u64, _u64, _vp, _vp, _vp]),
+    "kf_sparse_merge_tile": (_int, []),
+    "kf_sparse_merge_scratch_bytes": (_u64, [_u64, _u64]),
+    "kf_sparse_merge": (_int, [_vp, _vp, _int, _u64, _vp, _vp, _int, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
 }
 
 

@@ -539,6 +539,60 @@ class SparseCounter:
         return out
 
 
+def merge_tile() -> int:
+    """Merged positions per workgroup tile of kf_sparse_merge (a multiple of 64)."""
+    return int(N.lib().kf_sparse_merge_tile())
+
+
+def merge_scratch_bytes(n_a: int, n_b: int) -> int:
+    return int(N.lib().kf_sparse_merge_scratch_bytes(int(n_a), int(n_b)))
+
+
+def merge_sorted(keys_a: torch.Tensor, counts_a: torch.Tensor, keys_b: torch.Tensor, counts_b: torch.Tensor,
+                 stream: int | None = None):
+    """Enqueue kf_sparse_merge: the ascending union of two lists of (key, count)
+    on the device, equal keys' counts summed -- how a piece of a large file joins
+    its file's running result (main._merge_sorted_counts states what it computes).
+    keys_a / keys_b: contiguous int64 holding uint64 codes, each strictly ascending
+    in unsigned order (a genome's slice of SparseCounter.count); counts: int32
+    holding uint32, or int64, per side.  Returns (keys int64[n_a + n_b], counts
+    int64[n_a + n_b], n_out int64[1], status int32[1]) on the device: the first
+    n_out entries are the result, status is 1 (and n_out 0) if an input was not
+    strictly ascending.  The outputs and the scratch (16 B per tile) are allocated
+    here, on the current stream's pool; merged_to_host reads n_out and status."""
+    for k_, c_ in ((keys_a, counts_a), (keys_b, counts_b)):
+        assert k_.dtype == torch.int64 and k_.dim() == 1 and k_.is_contiguous()
+        assert c_.dtype in (torch.int32, torch.int64) and c_.shape == k_.shape and c_.is_contiguous()
+        assert k_.device == keys_a.device and c_.device == keys_a.device
+    dev = keys_a.device
+    n_a, n_b = keys_a.numel(), keys_b.numel()
+    keys = torch.empty(max(n_a + n_b, 1), dtype=torch.int64, device=dev)
+    counts = torch.empty(max(n_a + n_b, 1), dtype=torch.int64, device=dev)
+    n_out = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    need = merge_scratch_bytes(n_a, n_b)   # 0 above the library's limit: the call below says so
+    scratch = torch.empty(max(need // 8, 1), dtype=torch.int64, device=dev)
+    s = _stream_ptr(dev) if stream is None else stream
+    with torch.cuda.device(dev):
+        N.check(N.lib().kf_sparse_merge(
+            keys_a.data_ptr() if n_a else None, counts_a.data_ptr() if n_a else None,
+            4 if counts_a.dtype == torch.int32 else 8, n_a,
+            keys_b.data_ptr() if n_b else None, counts_b.data_ptr() if n_b else None,
+            4 if counts_b.dtype == torch.int32 else 8, n_b,
+            keys.data_ptr(), counts.data_ptr(), n_out.data_ptr(), status.data_ptr(), scratch.data_ptr(),
+            8 * scratch.numel(), s), "kf_sparse_merge")
+    return keys[: n_a + n_b], counts[: n_a + n_b], n_out, status
+
+
+def merged_to_host(n_out: torch.Tensor, status: torch.Tensor) -> int:
+    """merge_sorted's number of entries on the host (one copy for both words);
+    raises the library's error if the device's order check failed."""
+    n, st = torch.cat([n_out, status.to(torch.int64)]).cpu().tolist()
+    if st != 0:
+        raise N.NativeError("kf_sparse_merge: an input list is not strictly ascending (nothing was merged)")
+    return int(n)
+
+
 def counts_to_numpy(counts: torch.Tensor) -> np.ndarray:
     return counts.cpu().numpy().view(np.uint32)
 

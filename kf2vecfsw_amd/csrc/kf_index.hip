@@ -79,11 +79,10 @@ __global__ void __launch_bounds__(kIBlock) idx_scatter_kernel(const uint8_t* byt
 
 // ------------------------------------------------------------------ FASTQ
 // Scratch layout of kf_index_fastq, in 64-bit words (kf_index_fastq_scratch_bytes
-// is its size).  The two scans share one shape: level 1 turns 1,024 entries per
-// workgroup into exclusive prefixes in place and leaves a sum per workgroup,
-// level 2 does the same to those sums, level 3 (one workgroup) to level 2's.
-constexpr uint32_t kQLevel = 1024;   // entries per workgroup of a scan level
-constexpr uint64_t kQMaxEntries = (uint64_t)kQLevel * kQLevel * kQLevel;   // level 3 is one workgroup
+// is its size).  The two scans share one shape: the three levels of kf_scan.h.
+constexpr uint32_t kQLevel = kScanLevel;   // entries per workgroup of a scan level
+constexpr uint64_t kQMaxEntries = kScanMaxEntries;
+constexpr auto fq_scan_level_kernel = scan_level_kernel<uint64_t>;
 
 struct FqLayout {
     uint64_t nb, nb1, nb2;   // newline counts per block and their two levels of sums
@@ -133,22 +132,6 @@ __device__ __forceinline__ uint32_t thread_newlines(const uint8_t* bytes, uint64
 
 __global__ void __launch_bounds__(kIBlock) fq_count_kernel(const uint8_t* bytes, uint64_t end, uint64_t* blk) {
     compact_count((uint32_t)__builtin_popcount(thread_newlines(bytes, end, compact_p0())), blk);
-}
-
-// One scan level: workgroup i replaces v[i * 1024 + t] (entries below n) by their
-// exclusive prefix sums and writes their total to sums[i].
-__global__ void __launch_bounds__(kQLevel) fq_scan_level_kernel(uint64_t* v, uint64_t n, uint64_t* sums) {
-    __shared__ uint64_t wsum[kQLevel / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kQLevel + threadIdx.x;
-    uint64_t all;
-    const uint64_t ex = block_excl_scan<kQLevel / 64>(i < n ? v[i] : (uint64_t)0, wsum, &all);
-    if (i < n) v[i] = ex;
-    if (threadIdx.x == 0) sums[blockIdx.x] = all;
-}
-
-// entry i of a scanned table: its three levels added up
-__device__ __forceinline__ uint64_t scanned(const uint64_t* v, const uint64_t* s1, const uint64_t* s2, uint64_t i) {
-    return v[i] + s1[i >> 10] + s2[i >> 20];
 }
 
 __global__ void __launch_bounds__(kIBlock) fq_scatter_kernel(const uint8_t* bytes, uint64_t end, const uint64_t* blk,

@@ -1,8 +1,9 @@
 // kf_scan.h -- LDS and wave prefix-sum helpers shared by the device sources (also
 // by kf_sparse.hip, which does not use the count front end, kf_front.h): the wave
-// and workgroup scans, the one-workgroup scan with carry of the device pre-passes
-// and the per-thread search of a sorted table (kf_compact.h builds the pre-passes'
-// count -> scan -> scatter compaction on them).
+// and workgroup scans, the one-workgroup scan with carry of the device pre-passes,
+// the three-level scan of longer tables and the per-thread search of a sorted
+// table (kf_compact.h builds the pre-passes' count -> scan -> scatter compaction
+// on them).
 //
 // Every workgroup helper (block_excl_scan, block_sum, scan_with_carry, and
 // kf_compact.h's compact_count and compact_first_slot) must be reached by EVERY
@@ -108,6 +109,33 @@ __device__ __forceinline__ uint32_t scan_with_carry(uint32_t n, Load load, Store
         carry += tot;
     }
     return carry;
+}
+
+// A table too long for one workgroup is scanned in levels of kScanLevel entries
+// per workgroup (the FASTQ index's tables, the sorted merge's tile counts): level
+// 1 turns the entries of each workgroup into exclusive prefixes in place and
+// leaves a sum per workgroup, level 2 does the same to those sums, level 3 (one
+// workgroup) to level 2's; entry i of the scanned table is scanned(v, s1, s2, i).
+constexpr uint32_t kScanLevel = 1024;
+constexpr uint64_t kScanMaxEntries = (uint64_t)kScanLevel * kScanLevel * kScanLevel;   // level 3 is one workgroup
+
+// One scan level: workgroup i replaces v[i * 1024 + t] (entries below n) by their
+// exclusive prefix sums and writes their total to sums[i].
+namespace {
+template <typename T>
+__global__ void __launch_bounds__(kScanLevel) scan_level_kernel(T* v, uint64_t n, T* sums) {
+    __shared__ T wsum[kScanLevel / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kScanLevel + threadIdx.x;
+    T all;
+    const T ex = block_excl_scan<kScanLevel / 64>(i < n ? v[i] : T(0), wsum, &all);
+    if (i < n) v[i] = ex;
+    if (threadIdx.x == 0) sums[blockIdx.x] = all;
+}
+}  // namespace
+
+// entry i of a scanned table: its three levels added up
+__device__ __forceinline__ uint64_t scanned(const uint64_t* v, const uint64_t* s1, const uint64_t* s2, uint64_t i) {
+    return v[i] + s1[i >> 10] + s2[i >> 20];
 }
 
 // The last g in [0, n) with key(g) <= x, or 0 if there is none (key ascending).

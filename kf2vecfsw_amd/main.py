@@ -903,7 +903,10 @@ def record_pieces(path: str, piece: int | None = None) -> list[tuple[int, int]]:
 
 def _merge_sorted_counts(parts: list) -> tuple:
     """Union of per-piece (keys int64, counts) device tensors with equal keys'
-    counts summed (int64: a merged count may pass 2^32); keys ascending."""
+    counts summed (int64: a merged count may pass 2^32); keys ascending.  The
+    statement, in torch, of what kf_sparse_merge computes pair by pair
+    (counter.merge_sorted; keys below 2^63, where the signed sort is the unsigned
+    order): the tests compare the kernel with it, no product path calls it."""
     import torch
     keys = torch.cat([p[0] for p in parts])
     cnts = torch.cat([p[1].to(torch.int64) & 0xFFFFFFFF for p in parts])
@@ -1026,7 +1029,8 @@ def get_kmers(args) -> None:
     of the reference's 2..31): the sparse counter (device radix sort of every
     window's canonical code, kf_sparse_count); a FASTA file above SPLIT_BYTES
     goes through it in pieces (fasta_pieces) whose sorted results are merged on
-    the device, so no file size is refused.  The matrices are built on the
+    the device (kf_sparse_merge, one running result per file), so no file size
+    is refused.  The matrices are built on the
     device from the keys and counts (kf_kmers_rows) and streamed into the .npy
     files (_KmersNpyWriter); sparse_kmers_matrix / kmers_matrix above are the
     host statement of what it writes."""
@@ -1075,53 +1079,84 @@ def get_kmers(args) -> None:
             del counts
 
 
+MERGE_COPY_DOWN = 8   # a merged result is copied down when at least 1/8 of its storage is slack
+
+
 def _get_kmers_pieces(args, fasta_files: list[str], counter, device, budget: int, writer) -> None:
     """get_kmers' sparse path with files above SPLIT_BYTES: every file as its
-    fasta_pieces, the pieces in batches of at most `budget` bytes, a file's
-    piece results kept on the device until its last piece is counted, then
-    merged (_merge_sorted_counts) and written as main.py:147-176 does (the
-    merged int64 counts go to the row kernel as they are)."""
-    import torch
-    from .counter import pack_ranges, to_device
+    fasta_pieces, the pieces in batches of at most `budget` bytes.  Each
+    unfinished file has ONE running (keys, counts) on the device: its first
+    piece's slice of the batch's result as kf_sparse_count left it (u32 counts),
+    and from its second piece on the union of its pieces so far (u64 counts),
+    every further piece merged into it in file order straight from the batch's
+    result (counter.merge_sorted, kf_sparse_merge: two inputs and one output, no
+    sort).  The device so holds one running result per unfinished file plus one
+    batch, not every piece of a file plus a sort of all of them.  A merge's
+    output has room for n_a + n_b entries; when the pieces shared keys and at
+    least 1/MERGE_COPY_DOWN of that room is slack, the result is copied down to
+    its own size, so a running result never pins more than 8/7 of what it holds.
+    A file that finishes is written as main.py:147-176 does (u32 or u64 counts go
+    to the row kernel as they are); a file of one piece is written from the
+    batch's result with no merge.  A first piece whose file continues in the next
+    batch is the only slice that is copied out of a batch's result.
+    _merge_sorted_counts above states what the merges compute."""
+    from .counter import merge_sorted, merged_to_host, pack_ranges, to_device
     units = []                                    # (file index, start, end)
     for fi, p in enumerate(fasta_files):
         for a, e in fasta_pieces(p, args.k, SPLIT_BYTES):
             units.append((fi, a, e))
     last = {fi: j for j, (fi, _, _) in enumerate(units)}
-    pending: dict = {}
-    batch, size = [], 0
+    running: dict = {}                            # file index -> (keys, counts) of its pieces so far
+    batch, size, done = [], 0, 0
 
-    def run(batch):
+    def finish(fi):
+        k_, c_ = running.pop(fi)
+        base_name = os.path.basename(fasta_files[fi]).replace(".fna", "")   # main.py:127
+        writer.write([base_name], k_, c_, [0], [k_.numel()])
+
+    def run(batch, j_next):
+        """Count a batch, merge its pieces into their files' running results and
+        write the files whose last piece lies before unit j_next."""
+        nonlocal done
         hb = pack_ranges([(fasta_files[fi], a, e) for fi, a, e in batch], threads=host_threads(10))
         db = to_device(hb, device)
         keys, cnts, nu = counter.count(db, int(hb.off[-1]))
         nuh = counter.nuniq_to_host(nu)               # raises the library's error
+        views = set()                                 # files whose running result is a slice of keys / cnts
         for j, (fi, _, _) in enumerate(batch):
             lo, m = int(hb.off[j]), int(nuh[j])
-            pending.setdefault(fi, []).append((keys[lo: lo + m].clone(), cnts[lo: lo + m].clone()))
+            kb, cb = keys[lo: lo + m], cnts[lo: lo + m]
+            if fi not in running:
+                running[fi] = (kb, cb)
+                views.add(fi)
+                continue
+            ka, ca = running.pop(fi)
+            views.discard(fi)
+            k_, c_, n_out, status = merge_sorted(ka, ca, kb, cb)
+            del ka, ca
+            n = merged_to_host(n_out, status)         # raises the library's error
+            room = k_.numel()                         # n_a + n_b
+            k_, c_ = k_[:n], c_[:n]
+            if (room - n) * MERGE_COPY_DOWN >= room:
+                k_, c_ = k_.clone(), c_.clone()
+            running[fi] = (k_, c_)
+        while done < len(fasta_files) and last[done] < j_next:
+            finish(done)
+            views.discard(done)
+            done += 1
+        for fi in views:                              # continues in the next batch: let go of this batch's result
+            running[fi] = tuple(t.clone() for t in running[fi])
         del keys, cnts, nu, db, hb
 
-    def finish(fi):
-        k_, c_ = _merge_sorted_counts(pending.pop(fi))
-        base_name = os.path.basename(fasta_files[fi]).replace(".fna", "")   # main.py:127
-        writer.write([base_name], k_, c_, [0], [k_.numel()])
-
-    done = 0
     for j, u in enumerate(units):
         n = u[2] - u[1]
         if batch and size + n > budget:
-            run(batch)
+            run(batch, j)
             batch, size = [], 0
-            while done < len(fasta_files) and last[done] < j:
-                finish(done)
-                done += 1
         batch.append(u)
         size += (n + 15) // 16 * 16
     if batch:
-        run(batch)
-    while done < len(fasta_files):
-        finish(done)
-        done += 1
+        run(batch, len(units))
 
 
 # ---------------------------------------------------------------------------
