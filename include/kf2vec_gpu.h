@@ -352,6 +352,53 @@ int kf_sparse_merge(const uint64_t* d_keys_a, const void* d_counts_a, int count_
                     uint64_t* d_keys_out, uint64_t* d_counts_out, uint64_t* d_n_out,
                     uint32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- the chunk trainer's samples (kf2vec/datasets.py:27-101, Dataset_chunks_2rows:
+ * a contiguous run of a genome's window rows summed column-wise, divided by the
+ * grand total, times features_scaler) computed on the device from window count
+ * rows that stay there, for a whole table of samples per call:
+ *   d_counts         : n_rows x nbins counts, row-major; u16 (count_bytes = 2, the
+ *                      rows get_chunks keeps) or u32 (4, a kf_count_batch matrix)
+ *   d_lo[n_samples], d_n[n_samples] : sample s covers the rows [d_lo[s], d_lo[s] +
+ *                      d_n[s]); samples may overlap, repeat and be empty
+ *   cap              : counts enter as min(count, cap) (the reference's cap_data
+ *                      is 255); UINT32_MAX = no cap
+ *   d_out            : n_samples x nbins, float32 (out_bytes = 4) or float64 (8)
+ *   d_work           : kf_chunk_features_scratch_bytes(n_samples) bytes (a u64
+ *                      total per sample)
+ * With c_j = the sum of min(count, cap) over the sample's rows in column j and T
+ * = the sum of c_j over all columns, both exact integers (u16 and u32 rows are
+ * summed in 64 bits, for any d_n), d_out[s * nbins + j] = (double)c_j / (double)T
+ * * scaler in float64, every step rounded to nearest even (integers at or above
+ * 2^53 included, as numpy's astype(float64) rounds them), and rounded once more
+ * to float32 when out_bytes == 4: bit-equal to numpy's
+ * `s.astype(float64) / float64(T) * scaler` (and its `.astype(float32)`).  A
+ * sample with T == 0 (no rows, all zeros, cap == 0) is a row of +0.0, never NaN.
+ * Every element of d_out is written once; nothing outside it is.
+ * The table is checked on the device before anything is written: if for some s
+ * d_lo[s] + d_n[s] wraps or exceeds n_rows, then *d_status = 2 and no byte of
+ * d_out is written; otherwise *d_status = 0.  KF_EINVAL, before any HIP call,
+ * for count_bytes not 2 or 4, out_bytes not 4 or 8, nbins == 0, n_samples < 0, a
+ * scaler that is not finite, a null pointer (d_counts may be null when n_rows ==
+ * 0) or a misaligned one (count_bytes for d_counts, 8 bytes for d_lo, d_n and
+ * d_work, out_bytes for d_out, 4 for d_status).  KF_ERANGE if work_bytes <
+ * kf_chunk_features_scratch_bytes(n_samples); the message says what is needed.
+ * n_samples == 0 writes *d_status = 0 and nothing else.
+ * Threads run along the columns with 16-byte loads where nbins is a multiple of
+ * 16 / count_bytes and d_counts and d_out are 16-byte aligned (any other call
+ * takes a scalar path with the same result).  nbins <= 8192 (every k <= 7): one
+ * launch, a workgroup per sample sums its rows, reduces T and divides, the rows
+ * read once.  Larger nbins: one memset of the totals and two launches, the first
+ * adds (sample, column tile) sums to the sample's total with integer atomics
+ * (order-independent, so the result is deterministic), the second sums the rows
+ * again and divides.  Asynchronous on `stream`, no allocation, no host
+ * synchronisation, no workgroup waits for another; at most one memset and two
+ * kernel launches. */
+uint64_t kf_chunk_features_scratch_bytes(int32_t n_samples);
+int kf_chunk_features(const void* d_counts, int count_bytes, uint64_t n_rows, uint64_t nbins,
+                      const uint64_t* d_lo, const uint64_t* d_n, int32_t n_samples,
+                      uint32_t cap, double scaler, void* d_out, int out_bytes,
+                      uint32_t* d_status, void* d_work, uint64_t work_bytes, void* stream);
+
 /* Hash of the sources this library was built from (csrc/ + this header, as
  * kf2vecfsw_amd/build.py computes it): 16 hex digits, with a "+<tag>" suffix for
  * profiling builds.  The Python binding refuses a library whose id differs from

@@ -24,6 +24,10 @@ Here the genomes are processed in batches of files:
   the next launch (``kf_write_kf_segments16``: rows formatted by host threads,
   one file per genome written in parallel, appended when a genome's windows span
   several launches).
+
+``chunk_store`` runs the same pipeline without the writer and keeps the uint16
+rows on the device; ``ChunkStore.batch`` draws the chunk trainer's row runs and
+builds its batches there (``kf_chunk_features``, csrc/kf_chunkfeat.hip).
 """
 from __future__ import annotations
 
@@ -251,20 +255,14 @@ class ChunkPipeline:
         _tr("plan", t0, windows=sum(g.n_windows for g in genomes))
         return d_out
 
-    # ------------------------------------------------------------ count + write
-    def count_and_write(self, d_seq: torch.Tensor, genomes: list[Genome], output_dir: str) -> list:
-        """Gather, count and (asynchronously) write the windows of the batch's
-        kept genomes, at most max_windows per count launch.  Returns the futures
-        of the batch's writes."""
-        work = [g for g in genomes if g.excluded is None and g.write]
-        futs = []
-        if not work:
-            return futs
+    # ------------------------------------------------------------ count
+    def _count_launches(self, d_seq: torch.Tensor, work: list[Genome]):
+        """Gather and count the windows of `work` (genome after genome, one flat
+        window list), at most max_windows per count launch: yields (w0, w1, c16)
+        per launch, c16 the rows of the windows [w0, w1) on the device."""
         dev = self.device
-        # flat window list of the batch, with its genome boundaries
         starts = np.concatenate([g.starts for g in work]).astype(np.int64)
-        row0 = np.cumsum([0] + [g.n_windows for g in work])
-        total = int(row0[-1])
+        total = int(starts.size)
         d_starts = torch.from_numpy(starts).pin_memory().to(dev, non_blocking=True)
         stream = torch.cuda.current_stream(dev)
         for w0 in range(0, total, self.max_windows):
@@ -278,10 +276,33 @@ class ChunkPipeline:
             off = torch.arange(0, (nw + 1) * CHUNK_SZ, CHUNK_SZ, dtype=torch.int64, device=dev)
             db = DeviceBatch(self._wbuf, off, torch.zeros(2, dtype=torch.int64, device=dev), nw, 0)
             counts, _ = self.counter.count(db)
-            # a window has at most CHUNK_SZ - k + 1 < 2^16 k-mers: its counts cross
-            # PCIe as uint16 bit patterns (half the bytes of the u32 rows)
+            # a window has at most CHUNK_SZ - k + 1 < 2^16 k-mers: its counts are kept
+            # (and cross PCIe) as uint16 bit patterns, half the bytes of the u32 rows
             c16 = counts.to(torch.int16)
             del counts
+            yield w0, w1, c16
+            del c16
+
+    def count_rows(self, d_seq: torch.Tensor, genomes: list[Genome]) -> tuple[list[Genome], list[torch.Tensor]]:
+        """count_and_write without the write: the batch's kept genomes and their
+        window rows, int16 [windows, nbins] holding uint16 bit patterns, one tensor
+        per count launch, left on the device (genome after genome, as the .kf
+        files' rows would be)."""
+        work = [g for g in genomes if g.excluded is None and g.write]
+        return work, ([c16 for _, _, c16 in self._count_launches(d_seq, work)] if work else [])
+
+    # ------------------------------------------------------------ count + write
+    def count_and_write(self, d_seq: torch.Tensor, genomes: list[Genome], output_dir: str) -> list:
+        """Gather, count and (asynchronously) write the windows of the batch's
+        kept genomes, at most max_windows per count launch.  Returns the futures
+        of the batch's writes."""
+        work = [g for g in genomes if g.excluded is None and g.write]
+        futs = []
+        if not work:
+            return futs
+        row0 = np.cumsum([0] + [g.n_windows for g in work])
+        stream = torch.cuda.current_stream(self.device)
+        for w0, w1, c16 in self._count_launches(d_seq, work):
             done = torch.cuda.Event()
             done.record(stream)
             self.d2h.wait_event(done)
@@ -367,3 +388,147 @@ class ChunkPipeline:
     def close(self) -> None:
         self.drain()
         self.writer.shutdown()
+
+
+# ---------------------------------------------------------------------------
+# in-memory hand-off to the chunk trainer (kf_chunk_features)
+# ---------------------------------------------------------------------------
+def range_features_host(rows: np.ndarray, lo, n, scaler: float = 1.0, cap: int | None = None) -> np.ndarray:
+    """The numpy statement of kf_chunk_features (float64 [S, nbins]): sample s is
+    the column-wise sum of rows[lo[s]: lo[s] + n[s]] (whole-number counts, each as
+    min(count, cap) if `cap` is given) over its grand total, times `scaler` --
+    one view of Dataset_chunks_2rows (kf2vec/datasets.py:47-62; the numpy class
+    :143-157), NaN and inf of an all-zero run replaced by 0 as there.  The tests
+    compare the kernel with it; no product path calls it."""
+    rows = np.asarray(rows)
+    lo, n = np.asarray(lo).reshape(-1), np.asarray(n).reshape(-1)
+    out = np.empty((lo.size, rows.shape[1]), dtype=np.float64)
+    for s in range(lo.size):
+        r = rows[int(lo[s]): int(lo[s]) + int(n[s])].astype(np.uint64)
+        if cap is not None:
+            r = np.minimum(r, np.uint64(cap))
+        c = r.sum(axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            x = c.astype(np.float64) / np.float64(c.sum())
+        out[s] = np.nan_to_num(x, nan=0.0, posinf=0.0, neginf=0.0) * scaler
+    return out
+
+
+def draw_ranges(c, rng, views: int = 2) -> tuple[np.ndarray, np.ndarray]:
+    """The row runs Dataset_chunks_2rows draws (kf2vec/datasets.py:47-52, :74-79)
+    for items with c[i] window rows: (lo, n) int64 [len(c), views], run (i, v)
+    being the rows [lo, lo + n) of item i.  `rng` is a numpy.random.RandomState
+    or the numpy.random module; the draws are the reference's, item by item and
+    view by view: exponential(c / 5) for the length floor(draw) + 1, a
+    randint(1, c + 1) instead only if that passes c, then randint(0, c - n + 1)
+    for the start -- so a stream seeded like the reference's gives its runs."""
+    c = np.asarray(c, dtype=np.int64).reshape(-1)
+    if c.size and int(c.min()) < 1:
+        raise ValueError("draw_ranges: every item needs at least one row")
+    lo = np.empty((c.size, views), dtype=np.int64)
+    n = np.empty((c.size, views), dtype=np.int64)
+    for i, ci in enumerate(c.tolist()):
+        for v in range(views):
+            m = int(np.floor(rng.exponential(ci / 5)) + 1)
+            if m > ci:
+                m = int(rng.randint(low=1, high=ci + 1))
+            lo[i, v] = rng.randint(low=0, high=ci - m + 1)
+            n[i, v] = m
+    return lo, n
+
+
+@dataclass
+class ChunkStore:
+    """A directory's window count rows on the device, as train_model_set_chunks
+    holds them after my_read_csv_chunk (kf2vec/utils.py:402-405): genome g's rows
+    are counts[row0[g]: row0[g + 1]]."""
+    counts: torch.Tensor    # int16 [W, nbins] holding uint16 bit patterns, the kept genomes' rows back to back
+    row0: np.ndarray        # int64 [G + 1], host
+    samples: list           # G sample names
+    excluded: dict          # sample name -> "none" (no contig >= 10 kbp) or "few" (windows)
+    k: int
+
+    @classmethod
+    def from_host(cls, rows_per_genome, samples, k: int, device="cuda") -> "ChunkStore":
+        """A store of uint16 [windows, nbins] arrays, one per genome (the parsed rows of its .kf file)."""
+        from .counter import num_bins
+        nb = num_bins(k)
+        rows = [np.asarray(r) for r in rows_per_genome]
+        if len(rows) != len(samples):
+            raise ValueError("ChunkStore.from_host: {} genomes but {} sample names".format(len(rows), len(samples)))
+        for r, name in zip(rows, samples):
+            if r.dtype != np.uint16 or r.ndim != 2 or r.shape[1] != nb:
+                raise ValueError("ChunkStore.from_host: {}: rows must be uint16 [windows, {}] at k={}, got {} {}".format(
+                    name, nb, k, r.dtype, r.shape))
+        row0 = np.cumsum([0] + [r.shape[0] for r in rows]).astype(np.int64)
+        host = np.concatenate(rows) if rows else np.zeros((0, nb), np.uint16)
+        counts = torch.from_numpy(np.ascontiguousarray(host).view(np.int16)).to(torch.device(device))
+        return cls(counts, row0, list(samples), {}, k)
+
+    def batch(self, idx, rng, scaler: float = 1e4, cap: int | None = None, dtype: torch.dtype = torch.float32):
+        """One training batch: (Z [B, 2 * nbins], y int64 [B]) on the device for
+        the genomes idx, as Dataset_chunks_2rows gives them item by item
+        (kf2vec/datasets.py:91-93): Z[b] is two views of genome idx[b] side by
+        side (draw_ranges from `rng`, one kf_chunk_features call over the 2 B
+        runs), y = idx the label index."""
+        from .counter import chunk_features
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        lo, n = draw_ranges(self.row0[idx + 1] - self.row0[idx], rng)
+        lo += self.row0[idx][:, None]
+        z = chunk_features(self.counts, lo.reshape(-1), n.reshape(-1), scaler, cap, dtype)
+        return z.view(idx.size, 2 * self.counts.shape[1]), torch.from_numpy(idx).to(self.counts.device)
+
+
+def chunk_store(input_dir: str, k: int, device="cuda", batch_gb: float = 1.0, p=None) -> ChunkStore:
+    """The store `get_chunks -k k` on input_dir and parsing its .kf files would
+    give, without the files: the same input files (main.list_inputs), batches,
+    pre-pass, window plan and count launches (ChunkPipeline.prepare /
+    count_rows), every launch's uint16 rows kept on the device.  The genomes come
+    in input order; of files that share a sample name the last kept one stands,
+    at its place, as its .kf would have replaced the earlier one's; a genome
+    with no contig of 10 kbp or fewer than 5 windows is listed in `excluded`.
+    A file above main.SPLIT_BYTES is refused (ValueError) before anything is
+    counted: files counted in record parts are out of scope here."""
+    from . import main as M
+    from .counter import KmerCounter, pack_files
+    files_names, samples_names = M.list_inputs(input_dir)
+    paths = [os.path.join(input_dir, f) for f in files_names]
+    sizes = [os.path.getsize(q) for q in paths]
+    big = [f for f, s in zip(files_names, sizes) if s > M.SPLIT_BYTES]
+    if big:
+        raise ValueError("chunk_store: input file(s) above {} bytes are not supported (get_chunks counts them in "
+                         "record parts): {}".format(M.SPLIT_BYTES, ", ".join(big[:5])))
+    if k not in M.supported_k:
+        raise ValueError("k={} has no vocabulary: supported k are {}..{}".format(
+            k, M.supported_k.start, M.supported_k.stop - 1))
+    device = torch.device(device)
+    counter = KmerCounter(k, device)
+    budget = int(float(batch_gb or 1.0) * (1 << 30))
+    max_windows = max(1, min(budget // CHUNK_SZ, budget // (4 * counter.nbins), LAUNCH_WINDOWS))   # as get_chunks
+    threads = M.host_threads(p if p is not None else os.cpu_count() or 1)
+    pipe = ChunkPipeline(counter, device, max_windows, threads)
+    kept: dict = {}       # sample -> its rows, in the order of the files that stand
+    excluded: dict = {}
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        for idx in M._size_batches(sizes, min(budget, 3 << 30, max(sum(sizes) // 4, 16 << 20)), ramp=True):
+            hb = pack_files([paths[i] for i in idx], [samples_names[i] for i in idx], fmt=N.KF_FMT_FASTA, pool=pool)
+            genomes = [Genome(files_names[i], samples_names[i]) for i in idx]
+            d_seq = pipe.prepare(hb, genomes)
+            work, launches = pipe.count_rows(d_seq, genomes)
+            rows = torch.cat(launches) if launches else None
+            w0 = 0
+            for gm in work:
+                kept.pop(gm.sample, None)   # a later file of the same name replaces it
+                kept[gm.sample] = rows[w0: w0 + gm.n_windows]
+                w0 += gm.n_windows
+            for gm in genomes:
+                if gm.excluded is not None:
+                    excluded[gm.sample] = gm.excluded
+            del hb, d_seq
+    pipe.close()
+    samples = list(kept)
+    excluded = {s: why for s, why in excluded.items() if s not in kept}
+    row0 = np.cumsum([0] + [int(kept[s].shape[0]) for s in samples]).astype(np.int64)
+    counts = torch.cat([kept[s] for s in samples]) if samples else \
+        torch.zeros((0, counter.nbins), dtype=torch.int16, device=device)
+    return ChunkStore(counts.contiguous(), row0, samples, excluded, k)

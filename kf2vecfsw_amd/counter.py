@@ -623,6 +623,58 @@ def features(counts: torch.Tensor, pseudocount: bool = False, raw_cnt: bool = Fa
     return v * scaler if scaler != 1.0 else v
 
 
+def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | None = None,
+                   dtype: torch.dtype = torch.float32, out: torch.Tensor | None = None,
+                   stream: int | None = None) -> torch.Tensor:
+    """In-memory hand-off of get_chunks to the chunk trainer (kf_chunk_features):
+    [S, nbins] of `dtype` (float32 or float64), row s the column-wise sum of the
+    window rows counts[lo[s]: lo[s] + n[s]] (each count as min(count, cap) if
+    `cap` is given), divided by its grand total, times `scaler` -- what
+    Dataset_chunks_2rows computes per view (kf2vec/datasets.py:47-62), in float64
+    and rounded to float32 last; a sample with a zero total is a row of zeros.
+    chunks.range_features_host states it in numpy, bit for bit.
+
+    counts: contiguous [n_rows, nbins] on the device, int16 holding uint16 bit
+    patterns (ChunkStore.counts) or int32 holding uint32 (KmerCounter.count).
+    lo, n: host arrays (one staged pinned copy), or int64 tensors on the device.
+    The device checks the table; its status word is read back here (the call's
+    one synchronisation) and a sample outside [0, n_rows] raises N.NativeError
+    with `out` untouched."""
+    assert counts.dtype in (torch.int16, torch.int32) and counts.dim() == 2 and counts.is_contiguous()
+    assert dtype in (torch.float32, torch.float64)
+    dev = counts.device
+    if isinstance(lo, torch.Tensor) and lo.is_cuda:
+        assert isinstance(n, torch.Tensor) and n.device == lo.device == dev and lo.shape == n.shape
+        assert lo.dtype == n.dtype == torch.int64 and lo.is_contiguous() and n.is_contiguous()
+        d_lo, d_n = lo, n
+    else:
+        def as_i64(x):   # uint64 keeps its bit pattern
+            x = np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)
+            return x.view(np.int64) if x.dtype == np.uint64 else x.astype(np.int64)
+        t = torch.from_numpy(np.stack([as_i64(lo).reshape(-1), as_i64(n).reshape(-1)]))
+        d_lo, d_n = (t.pin_memory() if t.numel() else t).to(dev, non_blocking=True)
+    ns, nbins = d_lo.numel(), counts.shape[1]
+    if out is None:
+        out = torch.empty((ns, nbins), dtype=dtype, device=dev)
+    assert out.dtype == dtype and out.shape == (ns, nbins) and out.is_contiguous() and out.device == dev
+    if ns == 0:
+        return out
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    need = int(N.lib().kf_chunk_features_scratch_bytes(ns))
+    work = torch.empty(need // 8, dtype=torch.int64, device=dev)
+    s = _stream_ptr(dev) if stream is None else stream
+    with torch.cuda.device(dev):
+        N.check(N.lib().kf_chunk_features(
+            counts.data_ptr() if counts.shape[0] else None, counts.element_size(), counts.shape[0], nbins,
+            d_lo.data_ptr(), d_n.data_ptr(), ns, 0xFFFFFFFF if cap is None else int(cap), float(scaler),
+            out.data_ptr(), out.element_size(), status.data_ptr(), work.data_ptr(), need, s), "kf_chunk_features")
+    if stream is not None:   # the read-back below is ordered on torch's current stream only
+        torch.cuda.synchronize(dev)
+    if int(status.item()) != 0:
+        raise N.NativeError("kf_chunk_features: a sample's rows lie outside the count matrix (nothing was written)")
+    return out
+
+
 # ---------------------------------------------------------------------------
 # the get_kmers matrix on the device (kf_kmers_rows)
 # ---------------------------------------------------------------------------
