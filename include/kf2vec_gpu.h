@@ -399,6 +399,74 @@ int kf_chunk_features(const void* d_counts, int count_bytes, uint64_t n_rows, ui
                       uint32_t cap, double scaler, void* d_out, int out_bytes,
                       uint32_t* d_status, void* d_work, uint64_t work_bytes, void* stream);
 
+/* ---- get_chunks `.kf` text parsed on the device into the uint16 window rows the
+ * chunk trainers hold after my_read_csv_chunk (kf2vec/utils.py:402-405: pandas
+ * read_csv with dtype=uint16), for many files or pieces of files per call:
+ *   d_bytes, d_goff  : n_units units of text back to back (counter.pack_ranges'
+ *                      layout: 16-byte aligned, padded with '\n'); unit u is
+ *                      d_bytes[d_goff[u], d_goff[u+1]), a file or a piece of one
+ *                      cut at line starts.  Unit edges are taken from the offsets
+ *                      alone: a unit start is a line start and a unit end a line
+ *                      end whether a '\n' is there or not (a unit whose size is a
+ *                      multiple of 16 has no padding).
+ *   d_rows           : cap_rows x nbins, row-major
+ *   d_unit_row0      : n_units + 1 words: unit u's rows are [row0[u], row0[u+1])
+ *   d_status         : 4 words: code, unit, row within the unit, column
+ *   d_scratch        : kf_parse_kf_scratch_bytes(batch_bytes, n_units, cap_rows)
+ * Lines and rows: a line starts at a unit start or after a '\n' and ends before
+ * the next '\n' or at the unit end.  An empty line is no row (the padding makes
+ * such lines); every other line is a row, numbered in byte order.
+ * Fields: a row is a name followed by exactly nbins fields.  The name is every
+ * byte up to the row's first ',' (any bytes but ',' and '\n'; it may be empty and
+ * is not looked at); each field is preceded by ','.
+ * Field form: one or more decimal digits, then optionally '.' and zero or more
+ * '0'; the value is at most 65535 (accumulated so that a long digit string cannot
+ * wrap; leading zeros are fine).  That is what kf_write_kf_segments{,16} write
+ * without pseudocount ("16.0", or "16" for a row with no empty bin) and what
+ * my_read_csv_chunk reads without error.  It is NARROWER than pandas: exponents,
+ * signs, blanks, '\r' and fractions other than zeros are refused here, where
+ * pandas would accept some of them for other dtypes; get_chunks writes none.
+ * Results: d_rows[r * nbins + j] = field j of row r; d_unit_row0 as above; on
+ * success d_status[0..3] = 0.
+ * Errors: d_status[0] is the code of the error at the lowest byte offset,
+ *   1 too few fields   (column = the number of fields the row has; at the row end)
+ *   2 too many fields  (column = nbins; at the ',' that starts field nbins)
+ *   3 malformed field  (column = the field; at its first offending byte, an empty
+ *                       field's being the byte that ends it)
+ *   4 value above 65535 (column = the field; at the digit that passes it)
+ *   5 more rows than cap_rows (the row numbered cap_rows, column 0; rows from
+ *                       that one on are not parsed)
+ * with d_status[1] the unit, d_status[2] the row counted within the unit and
+ * d_status[3] the column.  After an error the contents of d_rows are
+ * unspecified (within its bounds); after code 5 the entries of d_unit_row0 are
+ * capped at cap_rows + 1.
+ * Memory safety: for any input bytes whatever, nothing outside d_rows[0, cap_rows
+ * * nbins), d_unit_row0[0, n_units], d_status[0, 4) and d_scratch is written and
+ * nothing outside d_bytes[0, batch_bytes) and d_goff[0, n_units] is read (unit
+ * ends are clamped to batch_bytes).
+ * KF_EINVAL, before any HIP call, for nbins == 0, n_units < 0, batch_bytes >=
+ * 2^32, a null pointer or a misaligned one (16 bytes for d_bytes, 2 for d_rows, 8
+ * for d_goff, d_unit_row0, d_status and d_scratch); KF_ERANGE if scratch_bytes is
+ * below kf_parse_kf_scratch_bytes (the message says what is needed), which is 16
+ * bytes + a word per 4 KiB of text + a word per row up to min(cap_rows,
+ * batch_bytes) and does not decrease when an argument grows.
+ * Five launches: the line starts of non-empty lines are compacted into a table
+ * (count per 4 KiB, scan, scatter), then workgroups take rows grid-stride, each
+ * walking its row in 4 KiB tiles of aligned 16-byte loads (a thread parses the
+ * fields that start in its 16 bytes), and one workgroup writes d_unit_row0 and
+ * the status.  A row is one workgroup's work, so few long rows (k >= 9) fill the
+ * device less than many short ones.  Asynchronous on `stream`, no allocation, no
+ * memset, no host synchronisation, no workgroup waits for another.
+ * Measured on one MI355X, 1 GiB of text resident (tools/kf_parse_bench.py,
+ * profiles/r14/): k=7 3.2 ms (335 GB/s of text; the text read three times plus
+ * the rows written = 0.21 of the kf_stream_probe rate), k=3 25.6 ms (0.03: a
+ * workgroup per 240-byte row); DESIGN.md section 4 has the table. */
+uint64_t kf_parse_kf_scratch_bytes(uint64_t batch_bytes, int32_t n_units, uint64_t cap_rows);
+int kf_parse_kf_rows(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n_units,
+                     uint64_t batch_bytes, uint64_t nbins, uint64_t cap_rows,
+                     uint16_t* d_rows, uint64_t* d_unit_row0, uint64_t* d_status,
+                     void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* Hash of the sources this library was built from (csrc/ + this header, as
  * kf2vecfsw_amd/build.py computes it): 16 hex digits, with a "+<tag>" suffix for
  * profiling builds.  The Python binding refuses a library whose id differs from

@@ -532,3 +532,174 @@ def chunk_store(input_dir: str, k: int, device="cuda", batch_gb: float = 1.0, p=
     counts = torch.cat([kept[s] for s in samples]) if samples else \
         torch.zeros((0, counter.nbins), dtype=torch.int16, device=device)
     return ChunkStore(counts.contiguous(), row0, samples, excluded, k)
+
+
+# ---------------------------------------------------------------------------
+# a get_chunks .kf directory as a ChunkStore (kf_parse_kf_rows)
+# ---------------------------------------------------------------------------
+KF_PIECE_BYTES = 1 << 30   # chunk_store_from_kf: .kf files above this go through in kf_line_pieces
+
+
+def _field_error(f: bytes) -> int:
+    """The first error of one field read left to right: 0 none, 3 malformed, 4 above 65535."""
+    v, st = 0, 0           # st: 0 no digit yet, 1 in the digits, 2 after the '.'
+    for c in f:
+        if 48 <= c <= 57:
+            if st == 2:
+                if c != 48:
+                    return 3
+                continue
+            v, st = v * 10 + (c - 48), 1
+            if v > 65535:
+                return 4
+        elif c == 46 and st == 1:
+            st = 2
+        else:
+            return 3
+    return 3 if st == 0 else 0
+
+
+def parse_kf_rows_host(data: bytes, nbins: int, cap_rows: int | None = None):
+    """The host statement of kf_parse_kf_rows for ONE unit of `.kf` text
+    (include/kf2vec_gpu.h has the contract): (rows uint16 [n, nbins], (code, row,
+    column)).  A line ends before a '\\n' or at the end of `data`; an empty line is
+    no row; a row is a name (every byte up to the first ',') and exactly nbins
+    fields, each one or more digits, optionally '.' and zeros, at most 65535.
+    (0, 0, 0) and every row if the text is fine; else the code of the error at
+    the lowest byte offset -- 1 too few fields (column: the fields there are), 2
+    too many (column nbins), 3 malformed field, 4 value above 65535, 5 a row
+    numbered cap_rows exists (column 0) -- with its row and column, and the rows
+    before that row.  The tests compare the kernel with it; no product path calls it."""
+    import re
+    nbins = int(nbins)
+    well = re.compile(rb"[^,]*(?:,[0-9]+(?:\.0*)?)*")
+    rows = []
+    for line in bytes(data).split(b"\n"):
+        if not line:
+            continue
+        r = len(rows)
+        if cap_rows is not None and r >= cap_rows:
+            return _rows_array(rows, nbins), (5, r, 0)
+        fields = line.split(b",")[1:]
+        if well.fullmatch(line) and len(fields) == nbins:      # the usual row, without a Python loop
+            v = np.asarray(fields, dtype="S").astype(np.float64) if fields else np.zeros(0)
+            if not (v > 65535).any():
+                rows.append(v.astype(np.uint16))
+                continue
+        for j, f in enumerate(fields):
+            if j >= nbins:
+                return _rows_array(rows, nbins), (2, r, nbins)
+            e = _field_error(f)
+            if e:
+                return _rows_array(rows, nbins), (e, r, j)
+        if len(fields) < nbins:
+            return _rows_array(rows, nbins), (1, r, len(fields))
+        raise AssertionError("parse_kf_rows_host: the two readings of a row disagree")
+    return _rows_array(rows, nbins), (0, 0, 0)
+
+
+def _rows_array(rows: list, nbins: int) -> np.ndarray:
+    return np.stack(rows) if rows else np.zeros((0, nbins), np.uint16)
+
+
+def kf_line_pieces(path: str, piece: int | None = None) -> list[tuple[int, int]]:
+    """Byte ranges [(a_i, e_i)] that cut a `.kf` file into parts of about `piece`
+    bytes at line starts, as main.record_pieces cuts FASTA at records: the parts
+    tile the file, every part but the first starts right after a '\\n', and a
+    single line longer than `piece` stays whole.  The last line needs no '\\n'."""
+    piece = KF_PIECE_BYTES if piece is None else int(piece)
+    size = os.path.getsize(path)
+    if size <= piece:
+        return [(0, size)]
+    cuts = [0]
+    with open(path, "rb") as f:
+        while cuts[-1] + piece < size:
+            pos = cuts[-1] + piece          # the first line start at or after pos
+            f.seek(pos - 1)
+            c = size
+            while True:
+                blk = f.read(1 << 20)
+                if not blk:
+                    break
+                i = blk.find(b"\n")
+                if i >= 0:
+                    c = f.tell() - len(blk) + i + 1
+                    break
+            if c >= size:
+                break
+            cuts.append(c)
+    return [(c, cuts[i + 1] if i + 1 < len(cuts) else size) for i, c in enumerate(cuts)]
+
+
+def chunk_store_from_kf(kf_dir: str, k: int, device="cuda", samples=None, batch_gb: float = 1.0, p=None) -> ChunkStore:
+    """The store of a directory of get_chunks `.kf` files (this tool's or the
+    reference's), as train_model_set_chunks holds them after my_read_csv_chunk
+    under mp.Pool (kf2vec/train_model_set_chunks.py:251-264), with the text parsed
+    on the device (kf_parse_kf_rows): what chunk_store gives for the FASTA files
+    the directory was made from, without them.
+
+    samples=None: every `*.kf` of kf_dir, sorted by name; else `<sample>.kf` for
+    each name in the order given (a missing file is a ValueError before anything
+    is read).  A file of no rows is listed in `excluded` as "none".  Files of any
+    size: one above KF_PIECE_BYTES goes through in kf_line_pieces.  The units
+    (files and pieces) are read in batches of about batch_gb GiB (a larger unit
+    alone, below 4 GiB) by pack_ranges on a reader thread, one batch ahead of the
+    device, into two pinned buffers in turn; each batch is copied to the device
+    and parsed there, and one small copy per batch brings its units' row counts
+    (and any refusal: a ValueError naming file, row and column) back.  The
+    batches' rows are joined by one torch.cat at the end, so the peak device
+    memory is the store plus its parts (twice the store) plus one batch."""
+    from . import main as M
+    from .counter import num_bins, pack_ranges, parse_kf_rows, parsed_to_host
+    if k not in M.supported_k:
+        raise ValueError("k={} has no vocabulary: supported k are {}..{}".format(
+            k, M.supported_k.start, M.supported_k.stop - 1))
+    if samples is None:
+        samples = sorted(f[:-3] for f in os.listdir(kf_dir) if f.endswith(".kf"))
+    samples = list(samples)
+    paths = [os.path.join(kf_dir, s + ".kf") for s in samples]
+    missing = [q for q in paths if not os.path.isfile(q)]
+    if missing:
+        raise ValueError("chunk_store_from_kf: no such file(s): {}".format(", ".join(missing[:5])))
+    device = torch.device(device)
+    nbins = num_bins(k)
+    budget = max(1, int(float(batch_gb or 1.0) * (1 << 30)))
+    threads = M.host_threads(p if p is not None else os.cpu_count() or 1)
+    units = [(fi, a, e) for fi, q in enumerate(paths) for a, e in kf_line_pieces(q, min(KF_PIECE_BYTES, budget))]
+    sizes = [e - a for _, a, e in units]
+    if sizes and max(sizes) >= (1 << 32) - 16:
+        raise ValueError("chunk_store_from_kf: {}: a single line of 4 GiB or more".format(
+            paths[units[int(np.argmax(sizes))][0]]))
+    batches = M._size_batches(sizes, budget)
+    padded = [sum((sizes[i] + 15) // 16 * 16 for i in b) for b in batches]
+    pin = device.type == "cuda"
+    bufs = [torch.empty(max(padded + [16]), dtype=torch.uint8, pin_memory=pin) for _ in range(min(2, len(batches)))]
+
+    def read(bi):
+        return pack_ranges([(paths[units[i][0]], units[i][1], units[i][2]) for i in batches[bi]], pin=pin,
+                           threads=threads, buf=bufs[bi % 2])
+
+    file_rows = [0] * len(paths)
+    parts = []
+    with ThreadPoolExecutor(max_workers=1) as reader:
+        nxt = reader.submit(read, 0) if batches else None
+        for bi, b in enumerate(batches):
+            hb = nxt.result()
+            # the other buffer's last copy (batch bi - 1) ended before that batch's row counts came back
+            nxt = reader.submit(read, bi + 1) if bi + 1 < len(batches) else None
+            nbytes = int(hb.off[-1])
+            d_bytes = hb.data[:max(nbytes, 16)].to(device, non_blocking=True)
+            rows, unit_row0, status = parse_kf_rows(d_bytes, hb.off, nbins)
+            names = [paths[units[i][0]] for i in b]
+            first = [min(x for x, j in enumerate(b) if units[j][0] == units[i][0]) for i in b]
+            row0 = parsed_to_host(unit_row0, status, names, [file_rows[units[i][0]] for i in b], first)
+            for x, i in enumerate(b):
+                file_rows[units[i][0]] += int(row0[x + 1] - row0[x])
+            parts.append(rows[: int(row0[-1])].clone())   # the batch's rows without the slack of its cap
+            del rows, d_bytes, hb
+    kept = [fi for fi in range(len(paths)) if file_rows[fi] > 0]
+    excluded = {samples[fi]: "none" for fi in range(len(paths)) if file_rows[fi] == 0}
+    row0 = np.cumsum([0] + [file_rows[fi] for fi in kept]).astype(np.int64)
+    counts = torch.cat(parts) if parts else torch.zeros((0, nbins), dtype=torch.int16, device=device)
+    del parts
+    return ChunkStore(counts.contiguous(), row0, [samples[fi] for fi in kept], excluded, k)

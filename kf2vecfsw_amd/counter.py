@@ -676,6 +676,84 @@ def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | 
 
 
 # ---------------------------------------------------------------------------
+# get_chunks .kf text parsed on the device (kf_parse_kf_rows)
+# ---------------------------------------------------------------------------
+KF_PARSE_ERRORS = {1: "too few fields", 2: "too many fields", 3: "malformed field", 4: "value above 65535",
+                   5: "more rows than the caller allowed for"}
+
+
+def parse_kf_rows(data: torch.Tensor, off, nbins: int, cap_rows: int | None = None, stream: int | None = None):
+    """Enqueue kf_parse_kf_rows: the get_chunks `.kf` text of a batch of units
+    (files, or pieces cut at line starts: chunks.kf_line_pieces) parsed into
+    uint16 window rows on the device, as my_read_csv_chunk leaves them
+    (kf2vec/utils.py:402-405).  chunks.parse_kf_rows_host states what it computes.
+
+    data: uint8 on the device, 16-byte aligned, the units back to back as
+    pack_ranges lays them out; off: the units' offsets [n + 1] (host array, or an
+    int64 tensor on the device); unit u is data[off[u]: off[u + 1]].
+    cap_rows: rows allowed for; by default (batch_bytes + n) // (2 * nbins + 1),
+    which no batch can exceed: a row is at least nbins times ',' and a digit, and
+    its '\n' unless it is its unit's last, so the rows stay below the batch's
+    own size (2 * nbins bytes of row for 2 * nbins + 1 of text).
+    Returns (rows int16 [cap_rows, nbins] holding uint16 bit patterns, unit_row0
+    int64 [n + 1], status int64 [4]) on the device: unit u's rows are
+    rows[unit_row0[u]: unit_row0[u + 1]]; parsed_to_host brings unit_row0 to the
+    host and raises what status says.  Outputs and scratch are allocated here."""
+    assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
+    dev = data.device
+    if isinstance(off, torch.Tensor) and off.is_cuda:
+        assert off.dtype == torch.int64 and off.is_contiguous() and off.device == dev
+        d_off = off
+        nbytes = int(off[-1].item()) if off.numel() else 0
+    else:
+        o = np.asarray(off.cpu() if isinstance(off, torch.Tensor) else off)
+        o = np.ascontiguousarray(o.view(np.int64) if o.dtype == np.uint64 else o.astype(np.int64))
+        nbytes = int(o[-1]) if o.size else 0
+        d_off = torch.from_numpy(o).to(dev)
+    n = max(d_off.numel() - 1, 0)
+    assert nbytes <= data.numel()
+    nbins = int(nbins)
+    if cap_rows is None:
+        cap_rows = (nbytes + n) // (2 * nbins + 1)
+    cap_rows = int(cap_rows)
+    rows = torch.empty((cap_rows, nbins), dtype=torch.int16, device=dev)
+    unit_row0 = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(4, dtype=torch.int64, device=dev)
+    need = int(N.lib().kf_parse_kf_scratch_bytes(nbytes, n, cap_rows))
+    scratch = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    one = torch.empty(8, dtype=torch.int16, device=dev)   # an address for the rows of a call that allows for none
+    s = _stream_ptr(dev) if stream is None else stream
+    with torch.cuda.device(dev):
+        N.check(N.lib().kf_parse_kf_rows(
+            data.data_ptr(), d_off.data_ptr(), n, nbytes, nbins, cap_rows,
+            rows.data_ptr() if rows.numel() else one.data_ptr(), unit_row0.data_ptr(), status.data_ptr(),
+            scratch.data_ptr(), 8 * scratch.numel(), s), "kf_parse_kf_rows")
+    return rows, unit_row0, status
+
+
+def parsed_to_host(unit_row0: torch.Tensor, status: torch.Tensor, names: Sequence[str] | None = None,
+                   row_base: Sequence[int] | None = None, first_unit: Sequence[int] | None = None) -> np.ndarray:
+    """parse_kf_rows' unit_row0 on the host (one copy for both tensors); raises
+    ValueError if the device refused the text, naming the unit's file (names[u],
+    else "unit u"), the row and the column, both counted from 0.  The row is
+    counted within the file when the caller says where the file began: unit
+    first_unit[u] is the first of this batch that belongs to u's file, and
+    row_base[u] rows of that file lie in batches before this one."""
+    both = torch.cat([status, unit_row0]).cpu().numpy()
+    code, unit, row, col = (int(x) for x in both[:4])
+    row0 = both[4:].copy()
+    if code != 0:
+        who = names[unit] if names is not None else "unit {}".format(unit)
+        if first_unit is not None:
+            row += int(row0[unit] - row0[first_unit[unit]])
+        if row_base is not None:
+            row += int(row_base[unit])
+        raise ValueError("{}: row {}, column {}: {} (kf_parse_kf_rows status {})".format(
+            who, row, col, KF_PARSE_ERRORS.get(code, "unknown error"), code))
+    return row0
+
+
+# ---------------------------------------------------------------------------
 # the get_kmers matrix on the device (kf_kmers_rows)
 # ---------------------------------------------------------------------------
 def kmers_tile_rows() -> int:
