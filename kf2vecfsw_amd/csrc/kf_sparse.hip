@@ -57,6 +57,7 @@ constexpr int kSWaves = kSBlock / 64;
 constexpr int kEB = 32;                        // emit: bytes per thread
 // LSD tiles (the overflow sort): 16384 u32 keys or 8192 u64 keys (the scatter
 // stages 64 KiB; profiles/r04/v49_*, v51_*).
+// TileOf::tile is restated in tests/test_gpu_sparse_structured.py (kTile4 / kTile8).
 template <typename KeyT>
 struct TileOf {
     static constexpr uint32_t tile = sizeof(KeyT) == 4 ? 16384u : 8192u;
@@ -69,12 +70,14 @@ constexpr uint32_t kTB = 16384;
 constexpr int kBBlock = (int)kTB / kEB;        // 512
 constexpr int kBWaves = kBBlock / 64;          // 8
 // Buckets: the top D bits of a 2k-bit key, D = min(10, 2k).
+// kBD is restated in tests/test_gpu_sparse_structured.py's plan model.
 constexpr int kBD = 10;
 constexpr uint32_t kNB = 1u << kBD;
 __host__ __device__ constexpr int sp_dbits(int k) { return 2 * k < kBD ? 2 * k : kBD; }
 // Phase C: 512-thread workgroups, chunks of at most 32 keys per thread (16,384:
 // 128 KiB of LDS for u64 keys), up to 256 VGPRs per thread (1024 threads spilled
 // at 128).
+// kCBlock x kCPer4 / kCPer8 (the chunk caps) are restated in tests/test_gpu_sparse_structured.py.
 constexpr int kCBlock = 512;
 constexpr int kCWaves = kCBlock / 64;
 constexpr int kCPer8 = 32;   // keys per thread, u64 keys
@@ -88,6 +91,7 @@ constexpr uint32_t kNoOvf = 0xFFFFFFFFu;
 // keys before the run fix-up.  Two 10-bit passes sort the top 20 bits, so a
 // 16,384-key chunk over 2^20 values leaves runs of equal top bits for ~1.6 % of
 // its keys (8-bit passes: ~22 %): k = 31 7.69 -> 7.23 ms (profiles/r05/v19_*).
+// kDB x kMsdPasses (the MSD-sorted top bits) are restated in tests/test_gpu_sparse_structured.py.
 constexpr int kMsdPasses = 2;
 constexpr int kDB = 10;
 constexpr uint32_t kND = 1u << kDB;          // digits
@@ -987,7 +991,7 @@ __global__ void __launch_bounds__(kCBlock) __attribute__((amdgpu_waves_per_eu(Ch
                     for (int it = 0; it < PER; ++it) y[it] = srow[it * 64];
                 }
             };
-            constexpr uint32_t kRun = 32;
+            constexpr uint32_t kRun = 32;   // restated in tests/test_gpu_sparse_structured.py
             for (int round = 0; round < 2; ++round) {
                 const bool msd = round == 0 && R > (uint32_t)(kDB * kMsdPasses);
                 const int lo = msd ? (int)R - kDB * kMsdPasses : 0;
