@@ -10,7 +10,9 @@
 //     byte spans, one per 1024-thread workgroup (16 waves); a span may cross
 //     genome boundaries;
 //   * each genome piece of a span is cut into 16 wave ranges; a wave walks its
-//     range with buffer loads (a register ring keeps the next loads in flight),
+//     range with buffer loads (a register ring keeps the next loads in flight;
+//     every load is cut at the last 1 KiB the range consumes, so the ring's
+//     run-ahead past a range end fetches nothing: x_range),
 //     classifies the bytes with v_perm / v_dot4 (no table loads), removes
 //     newlines, takes the k-1 bases of context from lane L-1 by DPP (lane 0
 //     from the wave's carry) and counts FORWARD k-mers into LDS; a k-mer and its
@@ -200,9 +202,11 @@ __device__ __forceinline__ uint32_t x_zmap(uint32_t x, uint32_t e, uint32_t c) {
 // 0 takes the previous region's lane 63.
 constexpr int kXNt = 2;   // buffer-load cache policy bit: non-temporal
 
-__device__ __forceinline__ XBlock xc_load(const uint8_t* bytes, uint64_t c0, uint32_t rel, uint32_t end_r, int lane) {
-    // clamped to the genome end rounded up to 16 B (load_chunk): bytes past it read 0
-    const uint32_t rec = end_r > rel ? min(end_r - rel, (uint32_t)kXChunk) : 0u;
+__device__ __forceinline__ XBlock xc_load(const uint8_t* bytes, uint64_t c0, uint32_t rel, uint32_t lim_r, int lane) {
+    // clamped to lim_r (x_range: the end of the wave's range in whole 1 KiB thirds,
+    // at most the genome end rounded up to 16 B as in load_chunk): bytes past it
+    // read 0 and a load wholly past it fetches nothing
+    const uint32_t rec = lim_r > rel ? min(lim_r - rel, (uint32_t)kXChunk) : 0u;
     const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(bytes + c0 + rel), (short)0, (int)rec, 0x00020000);
     XBlock b;
 #pragma unroll
@@ -530,8 +534,14 @@ __device__ __forceinline__ uint32_t x_range(const CountArgs& A, int32_t g, uint6
     uint32_t* gcounts = A.counts + (uint64_t)g * A.nbins;
     Range rg;
     rg.init(glo, ghi, lo, hi);
+    // The ring runs up to kXRing iterations ahead of the walk, so its last loads (and
+    // the first ones of a range shorter than the ring) lie past the range.  They
+    // are cut at the last 1 KiB third the range consumes: the slow path skips
+    // every third at or past nch, the fast path needs the whole iteration below
+    // hi_r <= nch * kChunk.  Wave-uniform, once per range: scalar code only.
+    const uint32_t lim_r = min(rg.end_r, rg.nch * (uint32_t)kChunk);
     auto load = [&](uint32_t r) {
-        return xc_load(A.bytes, rg.c0, r, rg.end_r, lane);
+        return xc_load(A.bytes, rg.c0, r, lim_r, lane);
     };
     // k <= 8: the ring as an array the compiler unrolls into registers; k = 9's
     // step is too large for that unroll, so its ring is two named blocks (an
