@@ -42,6 +42,7 @@
 #include <stdlib.h>
 
 #include <mutex>
+#include <utility>
 
 #include "kf_front.h"
 #include "kf_internal.h"
@@ -665,21 +666,250 @@ __device__ __forceinline__ void pair_f_sums_small(const uint32_t* hist, int tid,
     }
 }
 
-// Zero the 16-byte units [lo4, hi4) of the table (1024 threads).  The k <= 7
-// flush zeroes in two steps, each in the phase after the last read of its words:
-//   barrier 1 (adds done)       -> P and S are read into registers (F sums)
-//   barrier 2 (P and S read)    -> F and the drain flags are written to words
-//                                  [0, 4^k + 16); every word past them is dead
-//                                  and zeroed in the same phase
-//   barrier 3 (F, flags written)-> the columns and the flags are read
-//   barrier 4 (columns read)    -> F's words and the flags are zeroed
-//   barrier 5 (end of piece)    -> both zeroings are done: every wave finds P and S
-//                                  zero before its next add
-// No barrier can go: F overwrites words that other threads read for their sums
-// (2), is read across threads (3) and zeroed under its readers (4).
+// ---------------------------------------------------------------- the piece flush
+// Shared steps, the four bodies, then x_flush with the contract they all keep
+// (entry and exit state, reused LDS words, the barrier argument).
+//
+// Zero the 16-byte units [lo4, hi4) of the table (1024 threads).
 __device__ __forceinline__ void lds_zero(uint32_t* hist, uint32_t lo4, uint32_t hi4, int tid) {
     uint4* h4 = (uint4*)hist;
     for (uint32_t i = lo4 + (uint32_t)tid; i < hi4; i += kBlock) h4[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// The OR of the 16 waves' drain flags, LDS words f[0 .. 16) (16-byte aligned).
+__device__ __forceinline__ bool any_flag(const uint32_t* f) {
+    const uint4* fl = (const uint4*)f;
+    const uint4 f0 = fl[0], f1 = fl[1], f2 = fl[2], f3 = fl[3];
+    return (f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w | f2.x | f2.y | f2.z | f2.w | f3.x | f3.y | f3.z |
+            f3.w) != 0;
+}
+
+// k = 9: every column in order (coalesced row writes): its class's byte; rows
+// with carry corrections (already added to them) take atomics.
+__device__ __forceinline__ void flush_byte_classes(const CountArgs& A, uint32_t* hist, uint32_t* gc, bool whole,
+                                                   uint32_t drained, int tid, int lane, int wave) {
+    lds_barrier();   // every add of this piece is done
+    if (lane == 0) hist[XL<9>::P / 4 + wave] = drained;
+    lds_barrier();
+    const bool any_fix = any_flag(hist + XL<9>::P / 4);
+    const uint8_t* hb = (const uint8_t*)hist;
+    for (uint32_t c0 = (uint32_t)tid; c0 < (1u << 17); c0 += 4 * kBlock) {
+        uint32_t rep[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rep[j] = A.col2rep[c0 + j * kBlock];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t c = (rep[j] & 0x200u) ? kf_revcomp<9>(rep[j]) : rep[j];
+            const uint32_t v = hb[((c >> 1) & 0x1FE00u) | (c & 0x1FFu)];
+            if (whole && !any_fix)
+                __builtin_nontemporal_store(v, gc + c0 + j * kBlock);
+            else if (v)
+                __hip_atomic_fetch_add(gc + c0 + j * kBlock, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    lds_barrier();   // bytes read
+    lds_zero(hist, 0, XL<9>::bytes / 16, tid);
+}
+
+// k = 8: canonical 8-mer column = P[rep] + P[rc rep] (a palindrome once); drain
+// flags in the (unused) S area.
+__device__ __forceinline__ void flush_8mer_halves(const CountArgs& A, uint32_t* hist, uint32_t* gc, bool whole,
+                                                  uint32_t drained, int tid, int lane, int wave) {
+    lds_barrier();   // every add of this piece is done
+    if (lane == 0) hist[XL<8>::P / 4 + wave] = drained;
+    lds_barrier();
+    const bool any_drain = any_flag(hist + XL<8>::P / 4);
+    for (uint32_t col = tid; col < A.nbins; col += kBlock) {
+        const uint32_t y = A.col2rep[col], rc = kf_revcomp<8>(y);
+        uint32_t v = (hist[y >> 1] >> ((y & 1u) << 4)) & 0xFFFFu;
+        if (rc != y) v += (hist[rc >> 1] >> ((rc & 1u) << 4)) & 0xFFFFu;
+        if (whole && !any_drain)
+            gc[col] = v;
+        else if (v)
+            __hip_atomic_fetch_add(gc + col, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    lds_barrier();   // columns read
+    lds_zero(hist, 0, XL<8>::bytes / 16, tid);
+}
+
+// k <= 6: canonical column = F(rep) + F(rc rep) (a palindrome once, even k);
+// F = pair and single sums (pair_f_sums_small), back in LDS words [0, 4^k)
+// (swizzled as f_swz), the drain flags after them.
+template <int K>
+__device__ __forceinline__ void flush_small_pairs(const CountArgs& A, uint32_t* hist, uint32_t* gc, bool whole,
+                                                  uint32_t drained, int tid, int lane, int wave) {
+    constexpr uint32_t NY = 1u << (2 * K), NM = (NY + kBlock - 1) / kBlock;
+    constexpr uint32_t NCOL = (NY + (K % 2 == 0 ? (1u << K) : 0u)) / 2, NC = (NCOL + kBlock - 1) / kBlock;
+    constexpr uint32_t ZF = (NY + 16) / 4;   // 16-byte units of F and the 16 drain flags
+    static_assert(ZF <= XL<K>::bytes / 16, "F and the flags lie inside the table");
+    uint32_t rep[NC];
+#pragma unroll
+    for (uint32_t c = 0; c < NC; ++c) {
+        const uint32_t col = (uint32_t)tid + c * kBlock;
+        rep[c] = col < NCOL ? A.col2rep[col] : 0u;
+    }
+    lds_barrier();   // every add of this piece is done
+    uint32_t F[NM];
+    pair_f_sums_small<K>(hist, tid, F);
+    lds_barrier();   // P and S read
+#pragma unroll
+    for (uint32_t m = 0; m < NM; ++m) {
+        const uint32_t y = (uint32_t)tid + kBlock * m;
+        if (y < NY) hist[f_swz(y)] = F[m];
+    }
+    if (lane == 0) hist[NY + wave] = drained;   // (P holds 2 x 4^k words: past F is free)
+    // every word past F and the flags was read before the last barrier and
+    // is not touched again: zeroed here, off the end of the flush
+    lds_zero(hist, ZF, XL<K>::bytes / 16, tid);
+    lds_barrier();   // F in LDS words [0, 4^k), drain flags after it
+    const bool any_drain = any_flag(hist + NY);
+    uint32_t cv[NC];
+#pragma unroll
+    for (uint32_t c = 0; c < NC; ++c) {
+        const uint32_t y = rep[c], rc = kf_revcomp<K>(y);
+        cv[c] = hist[f_swz(y)] + (rc != y ? hist[f_swz(rc)] : 0u);
+    }
+    lds_barrier();   // columns and flags read: F's words can go
+    lds_zero(hist, 0, ZF, tid);
+#pragma unroll
+    for (uint32_t c = 0; c < NC; ++c) {
+        const uint32_t col = (uint32_t)tid + c * kBlock;
+        if (col >= NCOL) continue;
+        if (whole && !any_drain)
+            __builtin_nontemporal_store(cv[c], gc + col);
+        else if (cv[c])
+            __hip_atomic_fetch_add(gc + col, cv[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// k = 7: canonical column = F(rep) + F(rc rep), F = pair and single sums
+// (pair_f_sums and S), back in LDS words [0, 16384), the drain flags after them.
+__device__ __forceinline__ void flush_pair_table(const CountArgs& A, uint32_t* hist, uint32_t* gc, bool whole,
+                                                 uint32_t drained, int tid, int lane, int wave) {
+    // the columns' forward representatives, loaded before the barrier so
+    // their latency overlaps it.  A whole genome takes four consecutive
+    // columns per lane and 16-byte row stores (the flush is bound by the
+    // CU's store issue); other pieces one column per lane and atomics.
+    uint32_t rep[8];
+    // The columns' addresses are formed here, once per piece, from a copy of tid
+    // that the compiler cannot see through (no instruction).  From tid itself
+    // all 16 are hoisted out of the piece loop as 64-bit values that live across
+    // x_range's walk, which has no register to spare: called from x_flush, seven
+    // of them were spilled (80 bytes of scratch for 16).
+    int t = tid;
+    asm volatile("" : "+v"(t));
+    if (whole) {
+        const uint4 r0 = *(const uint4*)(A.col2rep + 4 * t), r1 = *(const uint4*)(A.col2rep + 4096 + 4 * t);
+        rep[0] = r0.x, rep[1] = r0.y, rep[2] = r0.z, rep[3] = r0.w;
+        rep[4] = r1.x, rep[5] = r1.y, rep[6] = r1.z, rep[7] = r1.w;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) rep[c] = A.col2rep[t + c * kBlock];
+    }
+    lds_barrier();   // every add of this piece is done
+    uint32_t F[16];
+    pair_f_sums(hist, tid, F);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {   // singles of y = 2048 i + 2 tid + {0, 1}
+        const uint32_t v = hist[XL<7>::P / 4 + i * 1024 + tid];
+        F[2 * i] += v & 0xFFFFu;
+        F[2 * i + 1] += v >> 16;
+    }
+    lds_barrier();   // P and S read
+#pragma unroll
+    for (int i = 0; i < 8; ++i) *(uint2*)(hist + f_swz(i * 2048 + 2 * tid)) = make_uint2(F[2 * i], F[2 * i + 1]);
+    if (lane == 0) hist[16384 + wave] = drained;   // (words past F are free now)
+    // the upper half of P and all of S (96 KiB less the flags) were read
+    // before the last barrier and are not touched again: zeroed here, so
+    // only F's 64 KiB are left for the end of the flush
+    constexpr uint32_t ZF = (16384 + 16) / 4;   // 16-byte units of F and the 16 drain flags
+    lds_zero(hist, ZF, XL<7>::bytes / 16, tid);
+    lds_barrier();   // F in LDS words [0, 16384), drain flags after it
+    const bool any_drain = any_flag(hist + 16384);
+    uint32_t cv[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const uint32_t y = rep[c], rc = kf_revcomp<7>(y);
+        cv[c] = hist[f_swz(y)] + hist[f_swz(rc)];
+    }
+    lds_barrier();   // columns and flags read: F's words can go
+    lds_zero(hist, 0, ZF, tid);
+    // the row writes last: their issue overlaps the zeroing, the barrier
+    // and the next piece's setup
+    if (whole && !any_drain) {
+        // non-temporal (k=7 -1.4 %; profiles/r03/v10_lib_ab_k*_nt_stores.json)
+        typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
+        __builtin_nontemporal_store(v4u_t{cv[0], cv[1], cv[2], cv[3]}, (v4u_t*)(gc + 4 * tid));
+        __builtin_nontemporal_store(v4u_t{cv[4], cv[5], cv[6], cv[7]}, (v4u_t*)(gc + 4096 + 4 * tid));
+    } else {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const uint32_t col = whole ? (c >> 2) * 4096 + 4 * tid + (c & 3) : tid + c * kBlock;
+            if (cv[c]) __hip_atomic_fetch_add(gc + col, cv[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// The flush of one genome piece: the workgroup's LDS counters of the piece go to
+// count row g (gc), and the table is left ready for the next piece.
+//
+// On entry: every wave of the workgroup has issued its LDS adds for this piece
+// and has passed no barrier since (so a wave may enter while others still
+// add).  `drained` is this wave's flag: one of its adds sent counts of this
+// piece to row g already (x_drain; k = 9: a byte carry corrected in the row).
+// `whole`: the piece is all of genome g and the call does not accumulate, so
+// nothing else writes row g, which the caller of the kernel zeroed.
+//
+// On exit: every count of the piece is in row g or on its way there (stores
+// and atomics issued; nothing reads them in this kernel).  A row that is
+// `whole` and that no wave drained was written with plain stores, any other
+// with atomic adds of its non-zero values: a drained row holds counts already,
+// a partial or accumulated one is shared.  The whole table and the flag words
+// are zero once the caller's closing lds_barrier() is passed; until then the
+// caller touches no LDS.
+//
+// LDS words the flush reuses (word = u32 index into hist):
+//   k <= 6  F(y) at f_swz(y) in [0, 4^k), the lower half of P; the 16 flags at
+//           [4^k, 4^k + 16), P's upper half (k = 2: exactly its last 16 words)
+//   k = 7   F at [0, 16384), the lower half of P; flags at [16384, 16400)
+//   k = 8, 9  no F; flags at [P / 4, P / 4 + 16), the start of the S area, which
+//           counting never touches at these k
+//
+// Barriers, k <= 7 (four in the flush, the fifth is the caller's):
+//   1 (adds done)        -> P and S are read into registers (the F sums)
+//   2 (P and S read)     -> F and the flags are written over words [0, 4^k + 16);
+//                           every word past them is dead and zeroed in this phase
+//   3 (F, flags written) -> the columns' F words and the flags are read
+//   4 (columns read)     -> F's words and the flags are zeroed; the row is written
+//   5 (end of piece)     -> both zeroings are done: every wave finds P and S zero
+//                           before its next add
+// None can go.  Without 1 a sum misses adds of a slower wave.  Without 2 a
+// thread's F overwrites P words that another thread has yet to sum (F lies in
+// P's lower half, and the sums are not owner-local).  Without 3 a column
+// reads F(rep), F(rc rep) and flags that other threads have not written: a
+// missed flag is a plain store over drained counts.  Without 4 the zeroing runs
+// under threads that still read F.  Without 5 a fast wave's adds for the next
+// piece land in words a slow thread then zeroes.  The zeroing cannot all move
+// to one phase either without a cost: after 2 only the words past F are dead,
+// and leaving them all for after 4 puts 160 KiB (k = 7), not 64, on the
+// flush's tail.  The row writes come last, after 4, so that their issue
+// overlaps the zeroing, barrier 5 and the next piece's setup.
+// k = 8, 9 (three in the flush): adds done -> flags written -> flags and
+// counters read (row written) -> whole table zeroed -> the caller's.  The flags
+// lie outside the counters, so the first of the three orders nothing that the
+// second does not; it stays because this code was moved as it stood, and
+// dropping it is a change to measure.  The other two are 3 and 4 above.
+template <int K>
+__device__ __forceinline__ void x_flush(const CountArgs& A, uint32_t* hist, uint32_t* gc, bool whole,
+                                        uint32_t drained, int tid, int lane, int wave) {
+    if constexpr (K == 9)
+        flush_byte_classes(A, hist, gc, whole, drained, tid, lane, wave);
+    else if constexpr (K == 8)
+        flush_8mer_halves(A, hist, gc, whole, drained, tid, lane, wave);
+    else if constexpr (K <= 6)
+        flush_small_pairs<K>(A, hist, gc, whole, drained, tid, lane, wave);
+    else
+        flush_pair_table(A, hist, gc, whole, drained, tid, lane, wave);
 }
 
 template <int K>
@@ -691,10 +921,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    {
-        uint4* h4 = (uint4*)hist;
-        for (uint32_t i = tid; i < XL<K>::bytes / 16; i += kBlock) h4[i] = make_uint4(0u, 0u, 0u, 0u);
-    }
+    lds_zero(hist, 0, XL<K>::bytes / 16, tid);
     __syncthreads();
     if ((uint32_t)(uintptr_t)(lds_u32*)hist != 0u) __builtin_trap();   // lds_add assumes base 0
     uint64_t span_lo, span_hi;
@@ -725,170 +952,9 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 
         const uint64_t lo = split_at_lattice(plo, phi, nit, lat, fr_lo), hi = split_at_lattice(plo, phi, nit, lat, fr_hi);
         uint32_t drained = 0;   // plain row stores unless a half was drained
         unsigned long long s = x_range<K>(A, g, glo, ghi, lo, hi, lane, iv_hint, drained);
-        uint32_t* gc = A.counts + (uint64_t)g * A.nbins;
-        // A whole genome in this span (the common case) with no drained half: no
-        // other workgroup and nothing else touches row g, which the caller
-        // zeroed, so it is written with plain stores; otherwise atomics.
+        // A whole genome in this span (the common case): see x_flush
         const bool whole = plo == glo && phi == ghi && !(A.flags & KF_ACCUMULATE);
-        if constexpr (K == 9) {
-            // every column in order (coalesced row writes): its class's byte;
-            // rows with carry corrections (already added to them) take atomics
-            lds_barrier();   // every add of this piece is done
-            if (lane == 0) hist[XL<K>::P / 4 + wave] = drained;
-            lds_barrier();
-            const uint4* fl = (const uint4*)(hist + XL<K>::P / 4);
-            const uint4 f0 = fl[0], f1 = fl[1], f2 = fl[2], f3 = fl[3];
-            const bool any_fix = (f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w | f2.x | f2.y | f2.z |
-                                  f2.w | f3.x | f3.y | f3.z | f3.w) != 0;
-            const uint8_t* hb = (const uint8_t*)hist;
-            for (uint32_t c0 = (uint32_t)tid; c0 < (1u << 17); c0 += 4 * kBlock) {
-                uint32_t rep[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) rep[j] = A.col2rep[c0 + j * kBlock];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t c = (rep[j] & 0x200u) ? kf_revcomp<9>(rep[j]) : rep[j];
-                    const uint32_t v = hb[((c >> 1) & 0x1FE00u) | (c & 0x1FFu)];
-                    if (whole && !any_fix)
-                        __builtin_nontemporal_store(v, gc + c0 + j * kBlock);
-                    else if (v)
-                        __hip_atomic_fetch_add(gc + c0 + j * kBlock, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            lds_barrier();   // bytes read
-            uint4* h4 = (uint4*)hist;
-            for (uint32_t i = tid; i < XL<K>::bytes / 16; i += kBlock) h4[i] = make_uint4(0u, 0u, 0u, 0u);
-        } else if constexpr (K == 8) {
-            // canonical 8-mer column = P[rep] + P[rc rep] (a palindrome once);
-            // drain flags in the (unused) S area
-            lds_barrier();   // every add of this piece is done
-            if (lane == 0) hist[XL<K>::P / 4 + wave] = drained;
-            lds_barrier();
-            const uint4* fl = (const uint4*)(hist + XL<K>::P / 4);
-            const uint4 f0 = fl[0], f1 = fl[1], f2 = fl[2], f3 = fl[3];
-            const bool any_drain = (f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w | f2.x | f2.y | f2.z |
-                                    f2.w | f3.x | f3.y | f3.z | f3.w) != 0;
-            for (uint32_t col = tid; col < A.nbins; col += kBlock) {
-                const uint32_t y = A.col2rep[col], rc = kf_revcomp<8>(y);
-                uint32_t v = (hist[y >> 1] >> ((y & 1u) << 4)) & 0xFFFFu;
-                if (rc != y) v += (hist[rc >> 1] >> ((rc & 1u) << 4)) & 0xFFFFu;
-                if (whole && !any_drain)
-                    gc[col] = v;
-                else if (v)
-                    __hip_atomic_fetch_add(gc + col, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            lds_barrier();   // columns read
-            uint4* h4 = (uint4*)hist;
-            for (uint32_t i = tid; i < XL<K>::bytes / 16; i += kBlock) h4[i] = make_uint4(0u, 0u, 0u, 0u);
-        } else if constexpr (K <= 6) {
-            // canonical column = F(rep) + F(rc rep) (a palindrome once, even k);
-            // F = pair and single sums (pair_f_sums_small), back in LDS words
-            // [0, 4^k) (swizzled as f_swz), the drain flags after them
-            constexpr uint32_t NY = 1u << (2 * K), NM = (NY + kBlock - 1) / kBlock;
-            constexpr uint32_t NCOL = (NY + (K % 2 == 0 ? (1u << K) : 0u)) / 2, NC = (NCOL + kBlock - 1) / kBlock;
-            constexpr uint32_t ZF = (NY + 16) / 4;   // 16-byte units of F and the 16 drain flags
-            static_assert(ZF <= XL<K>::bytes / 16, "F and the flags lie inside the table");
-            uint32_t rep[NC];
-#pragma unroll
-            for (uint32_t c = 0; c < NC; ++c) {
-                const uint32_t col = (uint32_t)tid + c * kBlock;
-                rep[c] = col < NCOL ? A.col2rep[col] : 0u;
-            }
-            lds_barrier();   // every add of this piece is done
-            uint32_t F[NM];
-            pair_f_sums_small<K>(hist, tid, F);
-            lds_barrier();   // P and S read
-#pragma unroll
-            for (uint32_t m = 0; m < NM; ++m) {
-                const uint32_t y = (uint32_t)tid + kBlock * m;
-                if (y < NY) hist[f_swz(y)] = F[m];
-            }
-            if (lane == 0) hist[NY + wave] = drained;   // (P holds 2 x 4^k words: past F is free)
-            // every word past F and the flags was read before the last barrier and
-            // is not touched again: zeroed here, off the end of the flush
-            lds_zero(hist, ZF, XL<K>::bytes / 16, tid);
-            lds_barrier();   // F in LDS words [0, 4^k), drain flags after it
-            const uint4* fl = (const uint4*)(hist + NY);
-            const uint4 f0 = fl[0], f1 = fl[1], f2 = fl[2], f3 = fl[3];
-            const bool any_drain = (f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w | f2.x | f2.y | f2.z | f2.w |
-                                    f3.x | f3.y | f3.z | f3.w) != 0;
-            uint32_t cv[NC];
-#pragma unroll
-            for (uint32_t c = 0; c < NC; ++c) {
-                const uint32_t y = rep[c], rc = kf_revcomp<K>(y);
-                cv[c] = hist[f_swz(y)] + (rc != y ? hist[f_swz(rc)] : 0u);
-            }
-            lds_barrier();   // columns and flags read: F's words can go
-            lds_zero(hist, 0, ZF, tid);
-#pragma unroll
-            for (uint32_t c = 0; c < NC; ++c) {
-                const uint32_t col = (uint32_t)tid + c * kBlock;
-                if (col >= NCOL) continue;
-                if (whole && !any_drain)
-                    __builtin_nontemporal_store(cv[c], gc + col);
-                else if (cv[c])
-                    __hip_atomic_fetch_add(gc + col, cv[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        } else {
-            // the columns' forward representatives, loaded before the barrier so
-            // their latency overlaps it.  A whole genome takes four consecutive
-            // columns per lane and 16-byte row stores (the flush is bound by the
-            // CU's store issue); other pieces one column per lane and atomics.
-            uint32_t rep[8];
-            if (whole) {
-                const uint4 r0 = *(const uint4*)(A.col2rep + 4 * tid), r1 = *(const uint4*)(A.col2rep + 4096 + 4 * tid);
-                rep[0] = r0.x, rep[1] = r0.y, rep[2] = r0.z, rep[3] = r0.w;
-                rep[4] = r1.x, rep[5] = r1.y, rep[6] = r1.z, rep[7] = r1.w;
-            } else {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) rep[c] = A.col2rep[tid + c * kBlock];
-            }
-            lds_barrier();   // every add of this piece is done
-            uint32_t F[16];
-            pair_f_sums(hist, tid, F);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {   // singles of y = 2048 i + 2 tid + {0, 1}
-                const uint32_t v = hist[XL<K>::P / 4 + i * 1024 + tid];
-                F[2 * i] += v & 0xFFFFu;
-                F[2 * i + 1] += v >> 16;
-            }
-            lds_barrier();   // P and S read
-#pragma unroll
-            for (int i = 0; i < 8; ++i) *(uint2*)(hist + f_swz(i * 2048 + 2 * tid)) = make_uint2(F[2 * i], F[2 * i + 1]);
-            if (lane == 0) hist[16384 + wave] = drained;   // (words past F are free now)
-            // the upper half of P and all of S (96 KiB less the flags) were read
-            // before the last barrier and are not touched again: zeroed here, so
-            // only F's 64 KiB are left for the end of the flush
-            constexpr uint32_t ZF = (16384 + 16) / 4;   // 16-byte units of F and the 16 drain flags
-            lds_zero(hist, ZF, XL<K>::bytes / 16, tid);
-            lds_barrier();   // F in LDS words [0, 16384), drain flags after it
-            const uint4* fl = (const uint4*)(hist + 16384);
-            const uint4 f0 = fl[0], f1 = fl[1], f2 = fl[2], f3 = fl[3];
-            const bool any_drain = (f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w | f2.x | f2.y | f2.z | f2.w |
-                                    f3.x | f3.y | f3.z | f3.w) != 0;
-            uint32_t cv[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint32_t y = rep[c], rc = kf_revcomp<7>(y);
-                cv[c] = hist[f_swz(y)] + hist[f_swz(rc)];
-            }
-            lds_barrier();   // columns and flags read: F's words can go
-            lds_zero(hist, 0, ZF, tid);
-            // the row writes last: their issue overlaps the zeroing, the barrier
-            // and the next piece's setup
-            if (whole && !any_drain) {
-                // non-temporal (k=7 -1.4 %; profiles/r03/v10_lib_ab_k*_nt_stores.json)
-                typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
-                __builtin_nontemporal_store(v4u_t{cv[0], cv[1], cv[2], cv[3]}, (v4u_t*)(gc + 4 * tid));
-                __builtin_nontemporal_store(v4u_t{cv[4], cv[5], cv[6], cv[7]}, (v4u_t*)(gc + 4096 + 4 * tid));
-            } else {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const uint32_t col = whole ? (c >> 2) * 4096 + 4 * tid + (c & 3) : tid + c * kBlock;
-                    if (cv[c]) __hip_atomic_fetch_add(gc + col, cv[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
+        x_flush<K>(A, hist, A.counts + (uint64_t)g * A.nbins, whole, drained, tid, lane, wave);
         s = wave_sum(s);
         if (lane == 0 && s) atomicAdd(A.totals + g, s);
         lds_barrier();    // P and S zero before the next piece's adds
@@ -1017,34 +1083,22 @@ using namespace kf;
 
 namespace {
 
-void* kernel_for(int k) {
-    switch (k) {
-    case 2: return (void*)&k1x_kernel<2>;
-    case 3: return (void*)&k1x_kernel<3>;
-    case 4: return (void*)&k1x_kernel<4>;
-    case 5: return (void*)&k1x_kernel<5>;
-    case 6: return (void*)&k1x_kernel<6>;
-    case 7: return (void*)&k1x_kernel<7>;
-    case 8: return (void*)&k1x_kernel<8>;
-    case 9: return (void*)&k1x_kernel<9>;
-    default: return nullptr;
-    }
-}
+constexpr int kK1xMaxK = 9;   // k1x_kernel<KF_MIN_K .. kK1xMaxK>; larger k: kf_bucket.hip
 
-// K1: histogram (4^k u32) + one u64 reduction slot per wave; K1x: P + S
-int lds_bytes_for(int k) {
-    switch (k) {
-    case 2: return (int)XL<2>::bytes;
-    case 3: return (int)XL<3>::bytes;
-    case 4: return (int)XL<4>::bytes;
-    case 5: return (int)XL<5>::bytes;
-    case 6: return (int)XL<6>::bytes;
-    case 7: return (int)XL<7>::bytes;
-    case 8: return (int)XL<8>::bytes;
-    default: return (int)XL<9>::bytes;
-    }
-}
+struct K1x {
+    void* fn;    // k1x_kernel<k>
+    int lds;     // its dynamic LDS bytes (P + S)
+};
 
+// the instantiation and LDS size for k, one table entry per I of the sequence
+template <int... I>
+const K1x* k1x_for(int k, std::integer_sequence<int, I...>) {
+    static const K1x table[] = {{(void*)&k1x_kernel<KF_MIN_K + I>, (int)XL<KF_MIN_K + I>::bytes}...};
+    return k >= KF_MIN_K && k <= kK1xMaxK ? &table[k - KF_MIN_K] : nullptr;
+}
+const K1x* k1x_for(int k) {   // nullptr for a k these kernels do not serve
+    return k1x_for(k, std::make_integer_sequence<int, kK1xMaxK - KF_MIN_K + 1>{});
+}
 
 // grid per (k, device): workgroups per CU from the occupancy API x CUs
 int g_grid[KF_MAX_K + 1][64];
@@ -1054,11 +1108,13 @@ int launch_info(int k, int* grid, int* block, int* lds) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return kf_fail(KF_EHIP, "hipGetDevice failed");
     if (dev < 0 || dev >= 64) return kf_fail(KF_EINVAL, "device index out of range");
-    const int l = lds_bytes_for(k);
+    const K1x* kx = k1x_for(k);
+    if (!kx) return kf_fail(KF_EINVAL, "no k <= 9 count kernel for this k");
+    const int l = kx->lds;
     std::lock_guard<std::mutex> lk(g_grid_mu);
     int& gr = g_grid[k][dev];
     if (!gr) {
-        void* fn = kernel_for(k);
+        void* fn = kx->fn;
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, l) != hipSuccess)
             return kf_fail(KF_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
         int per_cu = 0, cus = 0;
@@ -1128,7 +1184,7 @@ extern "C" int kf_count_batch(const uint8_t* d_bytes, const uint64_t* d_goff, in
     if (rc) return rc;
 
     void* args[] = {&A};
-    if (hipLaunchKernel(kernel_for(k), dim3(grid), dim3(block), args, (size_t)lds, s) != hipSuccess)
+    if (hipLaunchKernel(k1x_for(k)->fn, dim3(grid), dim3(block), args, (size_t)lds, s) != hipSuccess)
         return kf_fail(KF_EHIP, "count kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     return KF_OK;
 }
