@@ -467,6 +467,65 @@ int kf_parse_kf_rows(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n_u
                      uint16_t* d_rows, uint64_t* d_unit_row0, uint64_t* d_status,
                      void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- get_chunks `.kf` text formatted on the device: the inverse of
+ * kf_parse_kf_rows, and the lines of kf_write_kf_segments16 for raw counts
+ * (raw_cnt = 1; format_line in kf_host.cpp, main.py:344-357 and :905-915).
+ * Row r of d_counts[n_rows x nbins] (uint16) becomes one line; the lines stand
+ * back to back in d_text:
+ *   name ',' col_0 ',' ... ',' col_{nbins-1} '\n'
+ * name: prefix p = d_row_prefix[r], the bytes d_prefix_bytes[d_prefix_off[p],
+ * d_prefix_off[p + 1]) (any bytes, maybe none), followed, if win_len != 0, by
+ * dec(s + 1) '-' dec(s + win_len) for s = d_row_start[r] (uint64 arithmetic,
+ * wrapping); win_len == 0: the prefix alone, so a caller can pass whole names.
+ * column text of a count c: "c.5" with pseudocount, else "c.0"; without
+ * pseudocount a row with no zero column, or with only zero columns, is written
+ * as integer text "c" in every column (at k=3 nearly every 10 kbp window is).
+ * A line is at most name_len + 1 + 8 * nbins bytes ("65535.0,"), and a name at
+ * most its prefix + 41 bytes: callers size cap_bytes by that.
+ * d_row_off[r] = the byte offset of row r's line, d_row_off[n_rows] the total.
+ * d_status[0, 4) = code, bytes needed, row, 0:
+ *   0 ok (d_status[1] = the total)
+ *   1 the text is longer than cap_bytes: d_status[1] is the size needed,
+ *     d_row_off is still complete, the contents of d_text are unspecified
+ *     (within its bounds)
+ *   2 d_row_prefix[r] >= n_prefixes, or d_prefix_off is not non-decreasing:
+ *     d_status[2] is the first row whose prefix is out of range or has
+ *     d_prefix_off[p] > d_prefix_off[p + 1] (n_rows if the decreasing entries are
+ *     no row's prefix); nothing is formatted, d_row_off[n_rows] = 0 and the
+ *     other entries of d_row_off are unspecified.
+ * Memory safety, for any input whatever: nothing is written outside d_text[0,
+ * cap_bytes), d_row_off[0, n_rows], d_status[0, 4) and d_scratch; nothing is read
+ * outside d_counts[0, n_rows * nbins), d_prefix_off[0, n_prefixes], the prefix
+ * bytes of a call that is not refused, and d_row_prefix, d_row_start[0, n_rows).
+ * KF_EINVAL, before any HIP call, for nbins == 0, n_rows >= 2^31, cap_bytes >=
+ * 2^32 (offsets inside a call fit 32 bits: the caller cuts a launch's rows into
+ * calls), n_prefixes < 0, n_rows * nbins >= 2^42, a null pointer with n_rows > 0
+ * (d_row_off and d_status always), or a misaligned pointer (2 bytes for d_counts,
+ * 4 for d_row_prefix, 8 for d_prefix_off, d_row_start, d_row_off, d_status and
+ * d_scratch; d_text and d_prefix_bytes need none); KF_ERANGE if scratch_bytes is
+ * below kf_format_kf_scratch_bytes (the message says what is needed), which is
+ * 16 bytes + 16 per row + 8 per 2,048 cells and does not decrease when an
+ * argument grows.  n_rows == 0 is valid: d_row_off[0] = 0, status 0.
+ * Six launches (five with pseudocount): the prefix table is checked, a thread
+ * per row checks its prefix and stores its name's length, then the flat cell
+ * array is walked three times in tiles of 2,048 cells (8 per thread, whatever
+ * nbins is): the zero columns of every row (which decide its form), the text
+ * length of every tile, and -- after one workgroup scanned those -- the text,
+ * staged in LDS and stored as aligned 16-byte lines with byte stores at a
+ * tile's ragged ends.  Asynchronous on `stream`, no allocation, no memset, no
+ * host synchronisation, no workgroup waits for another.
+ * Measured on one MI355X, one count launch's rows (tools/kf_format_bench.py,
+ * profiles/r17/): k=7, 4,096 x 8,192 cells, 134 MB of text in 0.27 ms (500
+ * GB/s of text, 5.6 times a device copy of the text); k=3 0.037 ms; k=10, 511 x
+ * 524,800 cells, 1.07 GB in 1.64 ms; DESIGN.md section 4 has the table. */
+uint64_t kf_format_kf_scratch_bytes(uint64_t n_rows, uint64_t nbins);
+int kf_format_kf_rows16(const uint16_t* d_counts, uint64_t n_rows, uint64_t nbins,
+                        const uint8_t* d_prefix_bytes, const uint64_t* d_prefix_off, int32_t n_prefixes,
+                        const uint32_t* d_row_prefix, const uint64_t* d_row_start, uint32_t win_len,
+                        int pseudocount,
+                        uint8_t* d_text, uint64_t cap_bytes, uint64_t* d_row_off, uint64_t* d_status,
+                        void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* Hash of the sources this library was built from (csrc/ + this header, as
  * kf2vecfsw_amd/build.py computes it): 16 hex digits, with a "+<tag>" suffix for
  * profiling builds.  The Python binding refuses a library whose id differs from
@@ -543,6 +602,16 @@ int kf_write_kf_segments16(int32_t n_seg, const char* const* paths, const int32_
                            const uint64_t* row_start, uint32_t win_len,
                            const uint16_t* counts, uint64_t nbins, int pseudocount,
                            int raw_cnt, int n_threads);
+
+/* get_chunks' writer of finished text (kf_format_kf_rows16's, once on the host):
+ * segment g is text[seg_off[g], seg_off[g + 1]) (seg_off non-decreasing, n_seg +
+ * 1 entries), written to paths[g] (distinct) from the file's start, truncating
+ * it, or, if seg_append && seg_append[g], from its current end -- the meaning of
+ * kf_write_kf_segments.  Nothing is formatted: blocks of 4 MiB are written with
+ * pwrite at their file offsets by up to n_threads threads of the host pool.  An
+ * empty segment still creates or truncates its file. */
+int kf_write_text_segments(int32_t n_seg, const char* const* paths, const uint8_t* seg_append,
+                           const uint64_t* seg_off, const uint8_t* text, int n_threads);
 
 /* ---- get_chunks device pre-pass (replaces seqtk seq -l 0 | awk N-collapse |
  * seqkit seq -g -m, main.py:726-760).  d_seq holds n_rec sorted, disjoint

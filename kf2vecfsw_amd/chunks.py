@@ -23,7 +23,17 @@ Here the genomes are processed in batches of files:
   writer thread formats and writes each launch's rows while the device counts
   the next launch (``kf_write_kf_segments16``: rows formatted by host threads,
   one file per genome written in parallel, appended when a genome's windows span
-  several launches).
+  several launches);
+* at the k of ``DEVICE_FORMAT_K`` each launch's uint16 rows are instead formatted
+  into `.kf` text on the device
+  (``kf_format_kf_rows16``, csrc/kf_kfformat.hip); the used bytes of the text
+  come back on a copy stream of their own through two pinned slabs (a copier
+  thread), and a writer thread hands each slab's file ranges to
+  ``kf_write_text_segments`` (pwrite in parallel, one file per genome, appended
+  when a genome's windows span several slabs or launches) while the device
+  counts the next launch and the copier brings its text.
+  ``kf_write_kf_segments16`` (rows formatted by host threads) is the statement
+  the device formatter equals byte for byte (``format_rows_host``).
 
 ``chunk_store`` runs the same pipeline without the writer and keeps the uint16
 rows on the device; ``ChunkStore.batch`` draws the chunk trainer's row runs and
@@ -34,6 +44,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import queue
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
 
@@ -46,6 +57,14 @@ CHUNK_SZ = 10000       # main.py:100
 CHUNK_CNT_THR = 5      # main.py:101
 assert CHUNK_SZ < 1 << 16   # window counts fit uint16 (count_and_write)
 LAUNCH_WINDOWS = 4096  # windows per count launch at most (128 MiB of k=7 counts)
+# bytes of `.kf` text per pinned slab (count_and_write copies through two): a k=7 launch's text (134 MB) in
+# one, so that the native writer has all the launch's files to write side by side
+TEXT_SLAB = 144 << 20
+TEXT_SMALL = 4 << 20    # a piece of text up to this size travels in a pinned buffer of its own, not in a slab
+# k at which count_and_write formats on the device: where get_chunks measured no slower than with the host
+# formatter (profiles/r17: k=3 equal; k=7 0.79x and k=10 0.63x of the host writer's windows/s, whose 16
+# threads format while they wait for the files anyway; other k were not measured)
+DEVICE_FORMAT_K: frozenset = frozenset({3})
 
 # KF_TRACE=1: stage timeline (host ms since the first event) for tools/chunks_bench.py
 TRACE = os.environ.get("KF_TRACE") == "1"
@@ -185,6 +204,12 @@ class ChunkPipeline:
         # count rows go back on their own stream, so the next batch's H2D (on the
         # compute stream) overlaps them (PCIe is full duplex)
         self.d2h = torch.cuda.Stream(self.device)
+        # the device formatter's text: a copier thread brings it to two pinned slabs, which the writer gives back
+        self.copier = ThreadPoolExecutor(max_workers=1)
+        self._pin, self._pin_size = [None, None], [0, 0]
+        self._free = queue.SimpleQueue()
+        for b in range(2):
+            self._free.put(b)
 
     # ------------------------------------------------------------ pre-pass
     def prepare(self, hb, genomes: list[Genome]) -> torch.Tensor:
@@ -303,15 +328,6 @@ class ChunkPipeline:
         row0 = np.cumsum([0] + [g.n_windows for g in work])
         stream = torch.cuda.current_stream(self.device)
         for w0, w1, c16 in self._count_launches(d_seq, work):
-            done = torch.cuda.Event()
-            done.record(stream)
-            self.d2h.wait_event(done)
-            host = torch.empty(c16.shape, dtype=torch.int16, pin_memory=True)
-            with torch.cuda.stream(self.d2h):
-                host.copy_(c16, non_blocking=True)
-                c16.record_stream(self.d2h)
-                ev = torch.cuda.Event()
-                ev.record(self.d2h)
             # the segments of this launch: each genome's rows inside [w0, w1)
             segs = []
             for gi, g in enumerate(work):
@@ -320,10 +336,26 @@ class ChunkPipeline:
                     continue
                 segs.append((os.path.join(output_dir, g.out_name or "{}.kf".format(g.sample)), a - w0, b - w0, g,
                              a - int(row0[gi]), g.cont or a > int(row0[gi])))
-            args = self._write_args(segs)   # built here: the writer thread only formats + writes
+            args = self._write_args(segs)   # built here: the writer thread only formats or copies, and writes
             if len(self.pending) >= 2:      # at most two launches queued for the writer
                 self.pending.pop(0).result()
-            futs.append(self.writer.submit(self._write, ev, host, args))
+            # the text is made on the device where that measured no slower than the
+            # host formatter
+            if args is not None and self.counter.k in DEVICE_FORMAT_K:
+                q = queue.SimpleQueue()
+                self.copier.submit(self._copy_text, self._format_launch(c16, args), q)
+                futs.append(self.writer.submit(self._write_text, q, args))
+            else:
+                done = torch.cuda.Event()
+                done.record(stream)
+                self.d2h.wait_event(done)
+                host = torch.empty(c16.shape, dtype=torch.int16, pin_memory=True)
+                with torch.cuda.stream(self.d2h):
+                    host.copy_(c16, non_blocking=True)
+                    c16.record_stream(self.d2h)
+                    ev = torch.cuda.Event()
+                    ev.record(self.d2h)
+                futs.append(self.writer.submit(self._write, ev, host, args))
             self.pending.append(futs[-1])
             del c16
         return futs
@@ -355,6 +387,132 @@ class ChunkPipeline:
         arr = (ctypes.c_char_p * len(enc))(*enc)
         _tr("encode_names", t0, rows=int(rpos.size))
         return (len(first), paths, row0, app, enc, arr, rpre, rpos)
+
+    # ------------------------------------------------------------ device formatter
+    def _format_launch(self, c16: torch.Tensor, args) -> list:
+        """Enqueue kf_format_kf_rows16 for one launch's rows, in as many calls as
+        keep a call's text bound below 2^32, and the copy of every call's row
+        offsets and status to the host on the d2h stream.  Returns per call
+        (r0, r1, text, row_off + status on the host, its event)."""
+        import time
+        from .counter import KF_FORMAT_MAX_CAP, format_kf_row_bound, format_kf_rows
+        t0 = time.perf_counter()
+        _n_seg, _paths, _row0, _app, enc, _arr, rpre, rpos = args
+        dev = self.device
+        stream = torch.cuda.current_stream(dev)
+        n, nbins = int(c16.shape[0]), int(c16.shape[1])
+        bound = format_kf_row_bound(nbins, max(len(x) for x in enc), CHUNK_SZ)
+        per = max(1, KF_FORMAT_MAX_CAP // bound)
+        # the launch's name tables go to the device once
+        d_rpre = torch.from_numpy(rpre.view(np.int32)).to(dev, non_blocking=True)
+        d_rpos = torch.from_numpy(rpos.view(np.int64)).to(dev, non_blocking=True)
+        calls = []
+        for r0 in range(0, n, per):
+            r1 = min(n, r0 + per)
+            text, row_off, status = format_kf_rows(c16[r0:r1], enc, d_rpre[r0:r1], d_rpos[r0:r1], CHUNK_SZ,
+                                                   self.pseudocount)
+            done = torch.cuda.Event()
+            done.record(stream)
+            self.d2h.wait_event(done)
+            small = torch.empty(4 + r1 - r0 + 1, dtype=torch.int64, pin_memory=True)
+            with torch.cuda.stream(self.d2h):
+                small[:4].copy_(status, non_blocking=True)
+                small[4:].copy_(row_off, non_blocking=True)
+                for t in (text, row_off, status):
+                    t.record_stream(self.d2h)
+                ev = torch.cuda.Event()
+                ev.record(self.d2h)
+            calls.append((r0, r1, text, small, ev))
+        _tr("format_device", t0, rows=n, calls=len(calls))
+        return calls
+
+    def _copy_text(self, calls, q) -> None:
+        """One launch's text to the host (copier thread): per format call, once its
+        row offsets are on the host, the used bytes cross PCIe on the d2h stream
+        in pieces of at most TEXT_SLAB, each into a pinned slab that the writer has
+        given back (a piece of at most TEXT_SMALL bytes into a pinned buffer of its
+        own); q gets (r0, r1, row offsets, lo, hi, slab, event, host buffer) per
+        piece, then None (or the exception).  So the next launch's text is copied while
+        the writer writes this one's."""
+        import time
+        from .counter import format_status_check
+        try:
+            with torch.cuda.device(self.device):
+                for r0, r1, text, small, ev in calls:
+                    t0 = time.perf_counter()
+                    ev.synchronize()
+                    h = small.numpy()
+                    format_status_check(int(h[0]), int(h[1]), int(h[2]), int(text.numel()))
+                    off = h[4:]
+                    total = int(off[-1])
+                    _tr("wait_format", t0, bytes=total)
+                    for lo in range(0, total, TEXT_SLAB):
+                        hi = min(total, lo + TEXT_SLAB)
+                        if hi - lo <= TEXT_SMALL:         # (a launch's last few windows) no slab is held for it
+                            b, host = None, torch.empty(hi - lo, dtype=torch.uint8, pin_memory=True)
+                        else:
+                            b = self._free.get()          # a slab the writer is done with
+                            if self._pin[b] is None or self._pin[b].numel() < hi - lo:
+                                self._pin[b] = None       # grown at least 2x, up to the slab size
+                                self._pin[b] = torch.empty(min(TEXT_SLAB, max(hi - lo, 2 * self._pin_size[b])),
+                                                           dtype=torch.uint8, pin_memory=True)
+                                self._pin_size[b] = self._pin[b].numel()
+                            host = self._pin[b]
+                        done = torch.cuda.Event()
+                        with torch.cuda.stream(self.d2h):
+                            host[: hi - lo].copy_(text[lo:hi], non_blocking=True)
+                            done.record(self.d2h)
+                        q.put((r0, r1, off, lo, hi, b, done, host))
+            q.put(None)
+        except BaseException as e:   # the writer raises it
+            q.put(e)
+
+    def _write_text(self, q, args) -> None:
+        """One launch's text to its files (writer thread): every piece that the
+        copier queued, once it is on the host, goes to kf_write_text_segments as
+        the byte ranges of the files it covers."""
+        import time
+        n_seg, paths, row0, app, _enc, _arr, _rpre, _rpos = args
+        lib = N.lib()
+        started = [False] * n_seg          # a file is truncated (unless appended) by its segment's first range only
+        item = None
+        try:
+            while True:
+                item = q.get()
+                if item is None:
+                    return
+                if isinstance(item, BaseException):
+                    raise item
+                r0, r1, off, lo, hi, b, done, host = item
+                t1 = time.perf_counter()
+                done.synchronize()
+                _tr("text_d2h", t1, bytes=hi - lo)
+                t1 = time.perf_counter()
+                # the piece's segments: (segment, first byte, end byte), back to back
+                use = []
+                for g in range(n_seg):
+                    x, y = max(int(row0[g]), r0), min(int(row0[g + 1]), r1)
+                    if x < y:                  # (a segment has rows, and a row has bytes)
+                        x, y = max(int(off[x - r0]), lo), min(int(off[y - r0]), hi)
+                        if x < y:
+                            use.append((g, x, y))
+                cp = (ctypes.c_char_p * len(use))(*[paths[g] for g, _, _ in use])
+                ap = np.asarray([1 if (app[g] or started[g]) else 0 for g, _, _ in use], dtype=np.uint8)
+                so = np.asarray([use[0][1] - lo] + [y - lo for _, _, y in use], dtype=np.uint64)
+                for g, _, _ in use:
+                    started[g] = True
+                N.check(lib.kf_write_text_segments(len(use), cp, ap.ctypes.data, so.ctypes.data,
+                                                   host.data_ptr(), self.threads), "kf_write_text_segments")
+                if b is not None:
+                    self._free.put(b)
+                item = None
+                _tr("write_text", t1, segs=len(use), bytes=hi - lo)
+        finally:
+            # after an error: give back the slabs of the pieces that were not written, or the copier waits for ever
+            while item is not None and not isinstance(item, BaseException):
+                if item[5] is not None:
+                    self._free.put(item[5])
+                item = q.get()
 
     def _write(self, ev, host: torch.Tensor, args) -> None:
         """Format + write one launch's rows, once its counts are on the host."""
@@ -388,6 +546,7 @@ class ChunkPipeline:
     def close(self) -> None:
         self.drain()
         self.writer.shutdown()
+        self.copier.shutdown()
 
 
 # ---------------------------------------------------------------------------
@@ -538,6 +697,30 @@ def chunk_store(input_dir: str, k: int, device="cuda", batch_gb: float = 1.0, p=
 # a get_chunks .kf directory as a ChunkStore (kf_parse_kf_rows)
 # ---------------------------------------------------------------------------
 KF_PIECE_BYTES = 1 << 30   # chunk_store_from_kf: .kf files above this go through in kf_line_pieces
+
+
+def format_rows_host(rows: np.ndarray, prefixes, row_prefix, row_start, win_len: int, pseudocount: bool
+                     ) -> tuple[bytes, np.ndarray]:
+    """What kf_format_kf_rows16 computes, stated with the host formatter: the
+    lines of the uint16 rows back to back, and every line's offset (n + 1).  Row
+    r is main.format_kf(name, row, pseudocount, raw_cnt=True), the C++ formatter
+    that tests/golden/ref_postproc pins, named as Genome.names builds names:
+    prefixes[row_prefix[r]] (bytes, or str) followed, if win_len != 0, by
+    "<s+1>-<s+win_len>" for s = row_start[r] (uint64 arithmetic).  No product
+    path calls it."""
+    from .main import format_kf
+    rows = np.asarray(rows)
+    rows = rows.view(np.uint16) if rows.dtype == np.int16 else rows
+    pre = [x.decode(errors="surrogateescape") if isinstance(x, (bytes, bytearray)) else x for x in prefixes]
+    out, off = [], [0]
+    for r in range(rows.shape[0]):
+        name = pre[int(row_prefix[r])]
+        if win_len:
+            s = int(row_start[r])
+            name += "{}-{}".format((s + 1) % (1 << 64), (s + int(win_len)) % (1 << 64))
+        out.append(format_kf(name, rows[r].astype(np.uint32), bool(pseudocount), raw_cnt=True))
+        off.append(off[-1] + len(out[-1]))
+    return b"".join(out), np.asarray(off, dtype=np.int64)
 
 
 def _field_error(f: bytes) -> int:

@@ -754,6 +754,96 @@ def parsed_to_host(unit_row0: torch.Tensor, status: torch.Tensor, names: Sequenc
 
 
 # ---------------------------------------------------------------------------
+# get_chunks `.kf` text formatted on the device (kf_format_kf_rows16)
+# ---------------------------------------------------------------------------
+KF_FORMAT_ERRORS = {1: "the text is longer than the buffer allowed for",
+                    2: "a row's prefix is out of range, or the prefix offsets decrease"}
+KF_FORMAT_MAX_CAP = (1 << 32) - 1   # bytes of text per call (32-bit offsets inside a call)
+
+
+def format_kf_row_bound(nbins: int, max_prefix_len: int, win_len: int) -> int:
+    """Bytes that no line of format_kf_rows exceeds: the name (prefix, two uint64
+    in decimal and '-' if win_len), its ',' and 8 bytes per column ("65535.0,")."""
+    return int(max_prefix_len) + (41 if win_len else 0) + 1 + 8 * int(nbins)
+
+
+def format_kf_rows(counts16: torch.Tensor, prefixes, row_prefix, row_start, win_len: int, pseudocount: bool,
+                   stream: int | None = None, cap_bytes: int | None = None):
+    """Enqueue kf_format_kf_rows16: the uint16 window rows counts16 (int16 or
+    uint16 bit patterns, [n, nbins], on the device) as the `.kf` lines that
+    kf_write_kf_segments16 writes for raw counts, back to back.
+    chunks.format_rows_host states what it computes.
+
+    prefixes: the name prefixes (bytes, or str encoded as the writer encodes
+    them); row r is named prefixes[row_prefix[r]] followed by "<s+1>-<s+win_len>"
+    for s = row_start[r], or by nothing if win_len == 0.  row_prefix (uint32) and
+    row_start (uint64) are host arrays or tensors on the device.
+    cap_bytes: the size of the text buffer; by default n times
+    format_kf_row_bound, which no text exceeds (it must stay below 2^32: cut the
+    rows into calls).
+    Returns (text uint8 [cap_bytes], row_off int64 [n + 1], status int64 [4]) on
+    the device: row r's line is text[row_off[r]: row_off[r + 1]]; formatted_to_host
+    brings row_off to the host and raises what status says."""
+    assert counts16.dim() == 2 and counts16.is_contiguous() and counts16.element_size() == 2
+    dev = counts16.device
+    n, nbins = int(counts16.shape[0]), int(counts16.shape[1])
+    enc = [x if isinstance(x, (bytes, bytearray)) else x.encode(errors="surrogateescape") for x in prefixes]
+    pre_off = np.zeros(len(enc) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in enc], out=pre_off[1:])
+    blob = np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8)   # never empty: an address for no prefix bytes
+    d_pre = torch.from_numpy(blob.copy()).to(dev, non_blocking=True)
+    d_pre_off = torch.from_numpy(pre_off).to(dev, non_blocking=True)
+
+    def table(x, np_t, t_t):
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            assert x.dtype == t_t and x.is_contiguous() and x.device == dev and x.numel() == n
+            return x
+        h = np.ascontiguousarray(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x), dtype=np_t)
+        assert h.size == n
+        return torch.from_numpy(h.view(np.dtype(np_t).str.replace("u", "i"))).to(dev, non_blocking=True)
+
+    d_rpre = table(row_prefix, np.uint32, torch.int32)
+    d_rpos = table(row_start, np.uint64, torch.int64)
+    if cap_bytes is None:
+        cap_bytes = n * format_kf_row_bound(nbins, max([len(x) for x in enc], default=0), win_len)
+    cap_bytes = int(cap_bytes)
+    text = torch.empty(max(cap_bytes, 1), dtype=torch.uint8, device=dev)
+    row_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(4, dtype=torch.int64, device=dev)
+    need = int(N.lib().kf_format_kf_scratch_bytes(n, nbins))
+    scratch = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    s = _stream_ptr(dev) if stream is None else stream
+    with torch.cuda.device(dev):
+        N.check(N.lib().kf_format_kf_rows16(
+            counts16.data_ptr(), n, nbins, d_pre.data_ptr(), d_pre_off.data_ptr(), len(enc), d_rpre.data_ptr(),
+            d_rpos.data_ptr(), int(win_len), int(bool(pseudocount)), text.data_ptr(), cap_bytes, row_off.data_ptr(),
+            status.data_ptr(), scratch.data_ptr(), 8 * scratch.numel(), s), "kf_format_kf_rows16")
+    if stream is not None:   # the tables and the scratch are the caller's stream's until the call is done
+        for t in (d_pre, d_pre_off, d_rpre, d_rpos, scratch):
+            t.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+    return text[:cap_bytes], row_off, status
+
+
+def format_status_check(code: int, need: int, row: int, cap_bytes: int | None = None) -> None:
+    """Raise what kf_format_kf_rows16's status words say (nothing for code 0)."""
+    if code == 1:
+        raise N.NativeError("kf_format_kf_rows16: the text needs {} bytes{} (status 1)".format(
+            need, "" if cap_bytes is None else ", {} allowed for".format(cap_bytes)))
+    if code != 0:
+        raise ValueError("row {}: {} (kf_format_kf_rows16 status {})".format(
+            row, KF_FORMAT_ERRORS.get(code, "unknown error"), code))
+
+
+def formatted_to_host(row_off: torch.Tensor, status: torch.Tensor, cap_bytes: int | None = None) -> np.ndarray:
+    """format_kf_rows' row_off on the host (one copy for both tensors); raises
+    NativeError if the text did not fit and ValueError, naming the row (counted
+    from 0), if the device refused the prefix tables."""
+    both = torch.cat([status, row_off]).cpu().numpy()
+    format_status_check(int(both[0]), int(both[1]), int(both[2]), cap_bytes)
+    return both[4:].copy()
+
+
+# ---------------------------------------------------------------------------
 # the get_kmers matrix on the device (kf_kmers_rows)
 # ---------------------------------------------------------------------------
 def kmers_tile_rows() -> int:

@@ -863,6 +863,71 @@ extern "C" int kf_write_kf_segments16(int32_t n_seg, const char* const* paths, c
                           nbins, pseudocount, raw_cnt, n_threads);
 }
 
+// get_chunks' writer of text that is already formatted (kf_format_kf_rows16):
+// segment g is text[seg_off[g], seg_off[g + 1]), written to paths[g] from the
+// file's start (truncated) or, appended, from its current end.  The segments are
+// cut into blocks of kTextBlock bytes, each written by pwrite at its own file
+// offset on the host pool, the files side by side; nothing is formatted or
+// copied here.
+constexpr uint64_t kTextBlock = 4ull << 20;
+
+extern "C" int kf_write_text_segments(int32_t n_seg, const char* const* paths, const uint8_t* seg_append,
+                                      const uint64_t* seg_off, const uint8_t* text, int n_threads) {
+    if (n_seg < 0 || (n_seg && (!paths || !seg_off))) return kf_fail(KF_EINVAL, "null argument");
+    if (n_seg == 0) return KF_OK;
+    for (int32_t g = 0; g < n_seg; ++g)
+        if (seg_off[g + 1] < seg_off[g]) return kf_fail(KF_EINVAL, "seg_off must be non-decreasing");
+    if (seg_off[n_seg] > seg_off[0] && !text) return kf_fail(KF_EINVAL, "null argument");
+    if (n_threads < 1) n_threads = 1;
+    std::vector<int> fd((size_t)n_seg, -1);
+    std::vector<uint64_t> base((size_t)n_seg, 0);
+    auto close_all = [&]() {
+        bool ok = true;
+        for (int f : fd)
+            if (f >= 0) ok = (close(f) == 0) && ok;
+        return ok;
+    };
+    struct Block {
+        int32_t g;
+        uint64_t lo, hi;   // in text
+    };
+    std::vector<Block> blk;
+    for (int32_t g = 0; g < n_seg; ++g) {
+        const bool app = seg_append && seg_append[g];
+        fd[g] = open(paths[g], O_WRONLY | O_CREAT | (app ? 0 : O_TRUNC), 0666);
+        const off_t end = fd[g] >= 0 && app ? lseek(fd[g], 0, SEEK_END) : 0;
+        if (fd[g] < 0 || end < 0) {
+            close_all();
+            return kf_fail(KF_EINVAL, "cannot write %s", paths[g]);
+        }
+        base[g] = (uint64_t)end;
+        for (uint64_t lo = seg_off[g]; lo < seg_off[g + 1]; lo += kTextBlock)
+            blk.push_back({g, lo, std::min(lo + kTextBlock, seg_off[g + 1])});
+    }
+    // claim order: every segment at the same relative pace (as write_segments), so
+    // that concurrent workers hold different files (writes to one file serialise on
+    // its inode)
+    std::vector<std::pair<double, uint32_t>> order(blk.size());
+    for (size_t b = 0; b < blk.size(); ++b) {
+        const Block& B = blk[b];
+        order[b] = {((double)(B.lo - seg_off[B.g]) + 0.5) / (double)(seg_off[B.g + 1] - seg_off[B.g]), (uint32_t)b};
+    }
+    std::sort(order.begin(), order.end());
+    std::atomic<int32_t> bad{-1};
+    host_parallel(blk.size(), n_threads, [&](uint64_t i) {
+        const Block& B = blk[order[i].second];
+        if (bad.load() >= 0) return;
+        if (!pwrite_all(fd[B.g], (const char*)text + B.lo, B.hi - B.lo, base[B.g] + (B.lo - seg_off[B.g]))) {
+            int32_t none = -1;
+            bad.compare_exchange_strong(none, B.g);
+        }
+    });
+    const bool closed = close_all();
+    if (bad.load() >= 0) return kf_fail(KF_EINVAL, "cannot write %s", paths[bad.load()]);
+    if (!closed) return kf_fail(KF_EINVAL, "cannot close an output file");
+    return KF_OK;
+}
+
 extern "C" int kf_write_kf_rows(const char* path, const char* const* names, int32_t n, const uint32_t* counts,
                                 uint64_t nbins, int pseudocount, int raw_cnt, int n_threads) {
     if (!path || (!names && n) || (!counts && n) || n < 0) return kf_fail(KF_EINVAL, "null argument");
