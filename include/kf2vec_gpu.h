@@ -467,6 +467,95 @@ int kf_parse_kf_rows(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n_u
                      uint16_t* d_rows, uint64_t* d_unit_row0, uint64_t* d_status,
                      void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- get_frequencies `.kf` text parsed on the device into the float64 feature
+ * rows the trainers hold after my_read_csv (kf2vec/utils.py:436-437: pandas
+ * read_csv, index_col=0, header=None) and `* features_scaler`, for many files or
+ * pieces of files per call.  It follows kf_parse_kf_rows in everything but the
+ * field and the output: d_bytes, d_goff, units, lines and rows, the name, exactly
+ * nbins fields per row, d_unit_row0, d_status and its codes 1, 2, 3 and 5, "the
+ * error at the lowest byte offset wins", and the memory safety are as stated
+ * there.  What differs:
+ *   d_vals     : cap_rows x nbins values of val_bytes bytes, row-major: 8 float64,
+ *                4 float32
+ *   d_row_name : 2 x cap_rows uint32: d_row_name[2r] is the byte offset of row r's
+ *                name in the batch, d_row_name[2r + 1] its length (the bytes up to
+ *                the row's first ','); the caller takes the names from its own
+ *                copy of the text
+ *   d_scratch  : kf_parse_kf_floats_scratch_bytes(batch_bytes, n_units, cap_rows)
+ * Field form: digits [ '.' digits* ] [ ('e' | 'E') [ '+' | '-' ] digits ], with
+ * `digits` one or more decimal digits -- what repr(float64) and "%d" write -- or
+ * the three bytes "nan".  Signs on the significand, blanks, '\r', "inf",
+ * "NaN", hex and a significand that starts with '.' are refused (code 3 at the
+ * first offending byte): no writer of `.kf` files emits them.
+ * Value: the digits before and after the '.' are one decimal significand w;
+ * leading zeros (before or after the '.') are not significant.  From the first
+ * digit that is not '0' on, every digit counts -- a trailing run of zeros too,
+ * it is not folded into the exponent -- and there may be at most 19 of them, so
+ * w is exact in 64 bits (repr writes at most 17).  q is the explicit exponent
+ * minus the number of digits after the '.'; the exponent's magnitude saturates
+ * at 99999 and the count of fraction digits at 2^20, so no digit string wraps
+ * (either saturation leaves q outside the range below).  The field's value is
+ * the binary64 nearest to w * 10^q, ties to even -- Python's float(field), bit
+ * for bit -- by the Eisel-Lemire conversion of csrc/kf_decimal.h, which covers
+ * -342 <= q <= 308 and every uint64 w.  w == 0 gives 0.0 whatever q is; "nan"
+ * gives the quiet NaN 0x7FF8000000000000.
+ * Results: d_vals[r * nbins + j] = value * scaler, one float64 multiply (the
+ * trainers' `* features_scaler`), stored as float64 or rounded once more to
+ * float32 (to nearest even; above FLT_MAX it is infinite, as numpy's astype);
+ * d_row_name and d_unit_row0 as above; on success d_status[0..3] = 0.
+ * Errors: the codes of kf_parse_kf_rows but 4, which is not used, and
+ *   6 more than 19 significant digits (column = the field; at the digit that
+ *                       passes the limit)
+ *   7 magnitude outside the normal float64 range (column = the field; at the
+ *                       byte that ends it, before a code 2 at that byte): w != 0
+ *                       and w * 10^q below 2^-1022 -- subnormals are not
+ *                       produced, and a decimal just below 2^-1022 is not
+ *                       rounded up to it -- or rounding to more than DBL_MAX, or
+ *                       q outside [-342, 308]
+ * After an error the contents of d_vals and d_row_name are unspecified (within
+ * their bounds); a row without a ',' (code 1, column 0) has no name entry.
+ * Memory safety as kf_parse_kf_rows: nothing outside d_vals[0, cap_rows * nbins),
+ * d_row_name[0, 2 * cap_rows), d_unit_row0[0, n_units], d_status[0, 4) and
+ * d_scratch is written, for any input bytes whatever.
+ * KF_EINVAL, before any HIP call, for nbins == 0, n_units < 0, val_bytes other
+ * than 4 and 8, batch_bytes >= 2^32, a null pointer or a misaligned one (16
+ * bytes for d_bytes, val_bytes for d_vals, 4 for d_row_name, 8 for d_goff,
+ * d_unit_row0, d_status and d_scratch); KF_ERANGE if scratch_bytes is below
+ * kf_parse_kf_floats_scratch_bytes, which is kf_parse_kf_scratch_bytes plus the
+ * 10,416 bytes of the table of powers of five and does not decrease when an
+ * argument grows.
+ * One small copy and five launches: the table of powers of five (computed on the
+ * host on first use, once per process) is copied to the head of the scratch on
+ * `stream`, so a call leaves no state on the device; then kf_parse_kf_rows'
+ * passes with this field parser.  A row is one workgroup's work and a thread
+ * parses the fields that start in its 16 bytes: a float field is longer than
+ * that, so most threads parse one field or none, and a directory of thousands
+ * of genome rows fills the device where one row would not.  The launches are
+ * asynchronous on `stream`: no allocation, no memset, no wait for the device, no
+ * workgroup waits for another.  The copy of the table is a hipMemcpyAsync whose
+ * source is pageable host memory (the table never changes once built): the
+ * runtime stages its 10 KiB, so the host may wait for that staging copy, though
+ * not for the work queued on the device, and a stream that is being captured
+ * into a graph cannot take this call.
+ * Measured on one MI355X, 1 GiB of text resident (tools/kf_float_bench.py,
+ * profiles/r18/kf_float_k7.json): k=7, 5,839 rows, 7.1 ms (151 GB/s of text; 2.2
+ * times kf_parse_kf_rows' time per byte of text in the same run), k=3 30.0 ms
+ * (1.3 times), k=9 16.9 ms (4.1 times: 366 rows for 2,048 workgroup slots);
+ * DESIGN.md section 4 has the table. */
+uint64_t kf_parse_kf_floats_scratch_bytes(uint64_t batch_bytes, int32_t n_units, uint64_t cap_rows);
+int kf_parse_kf_floats(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n_units,
+                       uint64_t batch_bytes, uint64_t nbins, uint64_t cap_rows, double scaler,
+                       void* d_vals, int val_bytes, uint32_t* d_row_name,
+                       uint64_t* d_unit_row0, uint64_t* d_status,
+                       void* d_scratch, uint64_t scratch_bytes, void* stream);
+
+/* The conversion that kf_parse_kf_floats runs per field, on the host (the same
+ * inline code, csrc/kf_decimal.h): out[i] = the binary64 nearest to w[i] *
+ * 10^q[i], ties to even, and in_range[i] = 1; or in_range[i] = 0 and out[i] =
+ * 0.0 where the contract above reports code 7.  KF_EINVAL for a null pointer
+ * with n > 0. */
+int kf_decimal_to_double(const uint64_t* w, const int32_t* q, uint64_t n, double* out, uint8_t* in_range);
+
 /* ---- get_chunks `.kf` text formatted on the device: the inverse of
  * kf_parse_kf_rows, and the lines of kf_write_kf_segments16 for raw counts
  * (raw_cnt = 1; format_line in kf_host.cpp, main.py:344-357 and :905-915).

@@ -7,6 +7,7 @@ Layout:
   _native.py          ctypes binding of libkf2vec_gpu.so (no CPU fallback)
   counter.py          batch packing + KmerCounter (device counting)
   main.py             `get_frequencies` CLI mirror
+  features.py         a get_frequencies `.kf` directory as the trainers' float64 matrix
 """
 __all__ = ["__version__"]
 __version__ = "0.1.0"

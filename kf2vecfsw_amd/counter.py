@@ -679,7 +679,9 @@ def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | 
 # get_chunks .kf text parsed on the device (kf_parse_kf_rows)
 # ---------------------------------------------------------------------------
 KF_PARSE_ERRORS = {1: "too few fields", 2: "too many fields", 3: "malformed field", 4: "value above 65535",
-                   5: "more rows than the caller allowed for"}
+                   5: "more rows than the caller allowed for",
+                   # kf_parse_kf_floats' (features.parse_kf_floats), which has no code 4
+                   6: "more than 19 significant digits", 7: "magnitude outside the normal float64 range"}
 
 
 def parse_kf_rows(data: torch.Tensor, off, nbins: int, cap_rows: int | None = None, stream: int | None = None):
@@ -732,13 +734,15 @@ def parse_kf_rows(data: torch.Tensor, off, nbins: int, cap_rows: int | None = No
 
 
 def parsed_to_host(unit_row0: torch.Tensor, status: torch.Tensor, names: Sequence[str] | None = None,
-                   row_base: Sequence[int] | None = None, first_unit: Sequence[int] | None = None) -> np.ndarray:
+                   row_base: Sequence[int] | None = None, first_unit: Sequence[int] | None = None,
+                   what: str = "kf_parse_kf_rows") -> np.ndarray:
     """parse_kf_rows' unit_row0 on the host (one copy for both tensors); raises
     ValueError if the device refused the text, naming the unit's file (names[u],
     else "unit u"), the row and the column, both counted from 0.  The row is
     counted within the file when the caller says where the file began: unit
     first_unit[u] is the first of this batch that belongs to u's file, and
-    row_base[u] rows of that file lie in batches before this one."""
+    row_base[u] rows of that file lie in batches before this one.  `what` names
+    the call whose status this is (features.parse_kf_floats passes its own)."""
     both = torch.cat([status, unit_row0]).cpu().numpy()
     code, unit, row, col = (int(x) for x in both[:4])
     row0 = both[4:].copy()
@@ -748,8 +752,8 @@ def parsed_to_host(unit_row0: torch.Tensor, status: torch.Tensor, names: Sequenc
             row += int(row0[unit] - row0[first_unit[unit]])
         if row_base is not None:
             row += int(row_base[unit])
-        raise ValueError("{}: row {}, column {}: {} (kf_parse_kf_rows status {})".format(
-            who, row, col, KF_PARSE_ERRORS.get(code, "unknown error"), code))
+        raise ValueError("{}: row {}, column {}: {} ({} status {})".format(
+            who, row, col, KF_PARSE_ERRORS.get(code, "unknown error"), what, code))
     return row0
 
 
