@@ -556,6 +556,64 @@ int kf_parse_kf_floats(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n
  * with n > 0. */
 int kf_decimal_to_double(const uint64_t* w, const int32_t* q, uint64_t n, double* out, uint8_t* in_range);
 
+/* ---- tab-separated tables of decimal floats parsed on the device: the true
+ * distance matrix of a clade (`<tree>_subtree_<c>.di_mtrx`, read by both distance
+ * trainers with pandas read_csv(sep='\t', header=0, index_col=0) and reindexed by
+ * kf2vec/utils.py:141-192) and the backbone embeddings
+ * (`embeddings_subtree_<c>.csv`, kf2vec/query.py:129-134), for many pieces of a
+ * file per call.  The header line of a `.di_mtrx` is the caller's: the units hold
+ * the rows alone.  It follows kf_parse_kf_floats in everything not listed here:
+ * d_bytes, d_goff, units and their edges, lines and rows, empty lines,
+ * d_row_name, d_unit_row0, d_status and "the error at the lowest byte offset
+ * wins", the 19 significant digits, the value of a decimal, the memory safety for
+ * any input bytes, the scratch layout, the copy of the powers of five and the
+ * five launches, asynchronous on `stream` without allocation or host wait (and,
+ * for the copy's pageable source, not under graph capture).  What differs:
+ * Separator: '\t'.  The name is every byte up to the row's first '\t' (any bytes
+ * but '\t' and '\n': it may hold ',' and blanks and may be empty); each of the
+ * row's exactly `ncols` fields is preceded by '\t' (codes 1 and 2 as there, the
+ * column of code 2 being ncols).
+ * Field form: [ '-' ] digits [ '.' digits* ] [ ('e' | 'E') [ '+' | '-' ] digits ],
+ * or the three bytes "nan".  A '-' is taken only as a field's first byte; "-nan"
+ * (at its 'n'), a lone "-" (at the byte that ends it), "+1", "1-", "inf", blanks,
+ * ',' and '\r' are code 3 at the first offending byte.
+ * Value: the binary64 nearest to the decimal, ties to even, its sign bit set if
+ * the field began with '-': "-0.0" gives 0x8000000000000000.  There is no scaler.
+ * val_bytes == 4 rounds that value once more to float32, as numpy's astype.
+ * Columns: field j of row r goes to d_vals[r * out_cols + d_col_map[j]].
+ *   d_col_map : ncols int32 on the device.  An entry outside [0, out_cols) means
+ *               "skip this column": the field is still checked for form and digit
+ *               count (codes 3 and 6) but is not converted, so code 7 is never
+ *               reported for it.  NULL is the identity, and out_cols must then
+ *               equal ncols.
+ *   d_vals    : cap_rows x out_cols values of val_bytes bytes, row-major.  Entries
+ *               that no field maps to are not written (the caller pre-fills them);
+ *               two columns mapped to one destination leave it holding either
+ *               value.  Nothing outside d_vals[0, cap_rows * out_cols) is written,
+ *               whatever the map holds.
+ * Errors: codes 1, 2, 3, 5, 6 and 7 of kf_parse_kf_floats with the same columns
+ * (the file's column j, not its destination); no other code.
+ * KF_EINVAL, before any HIP call, for ncols == 0, out_cols == 0, d_col_map ==
+ * NULL with out_cols != ncols, n_units < 0, val_bytes other than 4 and 8,
+ * batch_bytes >= 2^32, a null pointer (but d_col_map) or a misaligned one (16
+ * bytes for d_bytes, val_bytes for d_vals, 4 for d_col_map and d_row_name, 8 for
+ * d_goff, d_unit_row0, d_status and d_scratch); KF_ERANGE if scratch_bytes is
+ * below kf_parse_tsv_floats_scratch_bytes, which equals
+ * kf_parse_kf_floats_scratch_bytes and does not decrease when an argument grows.
+ * A row is one workgroup's work, as there: an N x N matrix is N rows of about 19
+ * N bytes.  Measured on one MI355X (tools/tsv_bench.py,
+ * profiles/r19/tsv_floats.json): a 4,000 x 4,000 matrix, 301 MB of text resident,
+ * about 1.7 ms (170 GB/s of text), 1.8 ms with a shuffled map; three quarters of
+ * kf_parse_kf_floats' time per byte on k=7 text of the same size in the same run
+ * (whose 1,639 rows leave a fifth of the workgroup slots empty); DESIGN.md
+ * section 4 has the table. */
+uint64_t kf_parse_tsv_floats_scratch_bytes(uint64_t batch_bytes, int32_t n_units, uint64_t cap_rows);
+int kf_parse_tsv_floats(const uint8_t* d_bytes, const uint64_t* d_goff, int32_t n_units, uint64_t batch_bytes,
+                        uint64_t ncols, const int32_t* d_col_map, uint64_t out_cols, uint64_t cap_rows,
+                        void* d_vals, int val_bytes, uint32_t* d_row_name,
+                        uint64_t* d_unit_row0, uint64_t* d_status,
+                        void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* ---- get_chunks `.kf` text formatted on the device: the inverse of
  * kf_parse_kf_rows, and the lines of kf_write_kf_segments16 for raw counts
  * (raw_cnt = 1; format_line in kf_host.cpp, main.py:344-357 and :905-915).

@@ -8,6 +8,7 @@ Layout:
   counter.py          batch packing + KmerCounter (device counting)
   main.py             `get_frequencies` CLI mirror
   features.py         a get_frequencies `.kf` directory as the trainers' float64 matrix
+  tables.py           distance matrices and embedding tables (tab-separated floats) on the device
 """
 __all__ = ["__version__"]
 __version__ = "0.1.0"

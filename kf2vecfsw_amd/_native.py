@@ -76,6 +76,8 @@ SIGNATURES = {
     "kf_parse_kf_floats": (_int, [_vp, _vp, _i32, _u64, _u64, _u64, ctypes.c_double, _vp, _int, _vp, _vp, _vp, _vp, _u64,
                                   _vp]),
     "kf_decimal_to_double": (_int, [_vp, _vp, _u64, _vp, _vp]),
+    "kf_parse_tsv_floats_scratch_bytes": (_u64, [_u64, _i32, _u64]),
+    "kf_parse_tsv_floats": (_int, [_vp, _vp, _i32, _u64, _u64, _vp, _u64, _u64, _vp, _int, _vp, _vp, _vp, _vp, _u64, _vp]),
     "kf_format_kf_scratch_bytes": (_u64, [_u64, _u64]),
     "kf_format_kf_rows16": (_int, [_vp, _u64, _u64, _vp, _vp, _i32, _vp, _vp, _u32, _int, _vp, _u64, _vp, _vp, _vp, _u64,
                                    _vp]),

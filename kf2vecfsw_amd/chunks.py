@@ -785,16 +785,19 @@ def _rows_array(rows: list, nbins: int) -> np.ndarray:
     return np.stack(rows) if rows else np.zeros((0, nbins), np.uint16)
 
 
-def kf_line_pieces(path: str, piece: int | None = None) -> list[tuple[int, int]]:
+def kf_line_pieces(path: str, piece: int | None = None, start: int = 0) -> list[tuple[int, int]]:
     """Byte ranges [(a_i, e_i)] that cut a `.kf` file into parts of about `piece`
     bytes at line starts, as main.record_pieces cuts FASTA at records: the parts
     tile the file, every part but the first starts right after a '\\n', and a
-    single line longer than `piece` stays whole.  The last line needs no '\\n'."""
+    single line longer than `piece` stays whole.  The last line needs no '\\n'.
+    `start`: a line start to begin at (the parts tile the file from there on: a
+    table whose header line the caller read itself, tables.table_from_tsv)."""
     piece = KF_PIECE_BYTES if piece is None else int(piece)
     size = os.path.getsize(path)
-    if size <= piece:
-        return [(0, size)]
-    cuts = [0]
+    start = min(int(start), size)
+    if size - start <= piece:
+        return [(start, size)]
+    cuts = [start]
     with open(path, "rb") as f:
         while cuts[-1] + piece < size:
             pos = cuts[-1] + piece          # the first line start at or after pos

@@ -10,7 +10,7 @@
 // the power is needed only when the low 9 bits of the first product's high word
 // are all ones and that no case is left undecided after it, so there is no
 // fallback to a slower algorithm.  The same inline code is compiled for the
-// device (the kernels of kf_kffloat.hip) and for the host (kf_decimal_to_double
+// device (the kernels of kf_kffloat.hip and kf_tsvfloat.hip) and for the host (kf_decimal_to_double
 // in the same file, which the CPU tests call).
 //
 // Contract:
@@ -30,7 +30,7 @@
 // such that the top bit is set -- plus one in the last place for q >= -27 (where
 // 5^-q fits 64 bits and an exact quotient must be seen as exact), truncated
 // below that.  pow5_table_build computes it with schoolbook big-integer
-// arithmetic on the host, 13 ms once per process (kf_pow5_table in kf_kffloat.hip);
+// arithmetic on the host, 13 ms once per process (kf_pow5_table in kf_floatfield.h);
 // nothing is generated or stored.
 #pragma once
 #include <hip/hip_runtime.h>

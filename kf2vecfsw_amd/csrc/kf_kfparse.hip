@@ -46,6 +46,7 @@ struct CountField {
 // kf_kfrows.h's Sink: field j of row r goes to rows[r * nbins + j]; the name is not kept
 struct U16Sink {
     typedef CountField Field;
+    static constexpr uint32_t kSep = ',';
     uint16_t* __restrict__ rows;
     __device__ __forceinline__ Field fresh() const { return Field{0, 0}; }
     __device__ __forceinline__ void done(uint64_t r, uint64_t nbins, uint64_t col, const Field& f, bool store,

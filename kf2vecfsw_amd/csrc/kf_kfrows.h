@@ -1,14 +1,17 @@
-// kf_kfrows.h -- the passes that the two `.kf` readers share (kf_kfparse.hip:
+// kf_kfrows.h -- the passes that the readers of rows of text share (kf_kfparse.hip:
 // get_chunks rows of whole numbers into uint16; kf_kffloat.hip: get_frequencies
-// rows of decimal floats into float64 / float32).  Both read many units of text
-// back to back, unit u being d_bytes[goff[u], goff[u+1]), find the rows, walk
-// each row's fields and report the error at the lowest byte offset; they differ
-// in what a field is and where its value goes, which a Sink states:
+// rows of decimal floats into float64 / float32; kf_tsvfloat.hip: tab-separated
+// tables of signed decimal floats, the columns placed by a map).  All read many
+// units of text back to back, unit u being d_bytes[goff[u], goff[u+1]), find the
+// rows, walk each row's fields and report the error at the lowest byte offset;
+// they differ in the separator, in what a field is and in where its value goes,
+// which a Sink states (below, "','" stands for the Sink's separator):
 //
 //   struct Sink {
+//       static constexpr uint32_t kSep;   // the byte between the name and the fields: ',' or '\t'
 //       typedef ... Field;            // one field's state, with
 //                                     //   int feed(uint32_t c): 0 go on, 1 the field
-//                                     //   ended well (c is ',' or '\n'), else the code
+//                                     //   ended well (c is kSep or '\n'), else the code
 //       Field fresh() const;          // the state before a field's first byte
 //       // field `col` of row r ended well: store its value if `store`, or note
 //       // (into err) the code that the value itself earns
@@ -207,7 +210,7 @@ __device__ __forceinline__ uint64_t parse_row(const uint8_t* __restrict__ bytes,
                 if (x < s || x >= lim) continue;
                 const uint32_t c = byte_of(w, q);
                 valid |= 1u << q;
-                cm |= (c == ',' ? 1u : 0u) << q;
+                cm |= (c == Sink::kSep ? 1u : 0u) << q;
                 nm |= (c == '\n' ? 1u : 0u) << q;
             }
         }
@@ -232,7 +235,7 @@ __device__ __forceinline__ uint64_t parse_row(const uint8_t* __restrict__ bytes,
                         else note(err, col, e);
                     }
                 }
-                if (c == ',') {
+                if (c == Sink::kSep) {
                     if (j == 0) sink.name(r, (uint32_t)s, (uint32_t)(p + q - s), store);
                     if (j >= nbins) {
                         note(err, nbins, kErrMany);
