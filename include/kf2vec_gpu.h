@@ -673,6 +673,107 @@ int kf_format_kf_rows16(const uint16_t* d_counts, uint64_t n_rows, uint64_t nbin
                         uint8_t* d_text, uint64_t cap_bytes, uint64_t* d_row_off, uint64_t* d_status,
                         void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- tables of floats formatted on the device: the inverse of
+ * kf_parse_kf_floats and kf_parse_tsv_floats, and the text of query's two
+ * tables (kf2vec/query.py:178-192: .tolist() and csv.writer), of the trainers'
+ * to_csv tables of float32 frames (train_model_set.py:630-643) and of `.di_mtrx`
+ * files.  Row r of d_vals[n_rows x ncols] (float32 or float64 by val_bytes, row
+ * major) becomes one line; the lines stand back to back in d_text:
+ *   prefix_r sep f_0 sep ... sep f_{ncols-1} eol
+ * prefix_r: the bytes d_prefix_bytes[d_prefix_off[p], d_prefix_off[p + 1]) for p
+ * = d_row_prefix[r] (any bytes: the host quotes labels before it passes them);
+ * an empty prefix writes no leading separator.  sep: one byte, not NUL.  eol:
+ * eol_len = 1 or 2 bytes, the first in the low byte of `eol` ("\r\n" = 0x0A0D:
+ * csv.writer; "\n" = 0x0A: pandas).
+ * f: the shortest decimal that reads back as the value (csrc/kf_shortest.h:
+ * Schubfach), of the shortest candidates the closest, at most 24 bytes:
+ *   mode KF_FLOAT_SHORTEST, val_bytes 8   Python's repr(float)
+ *   mode KF_FLOAT_SHORTEST, val_bytes 4   numpy's str(np.float32) (at most 9
+ *                                         digits), which is also pandas' to_csv
+ *   mode KF_FLOAT_WIDENED,  val_bytes 4   repr of the float32 converted to
+ *                                         double: .tolist() then csv.writer
+ * Fixed notation for 1e-4 <= |v| < 1e16 (repr decides by the decimal's exponent,
+ * numpy by the value: float32(1e-4) is "1e-04"), integral values with ".0", else
+ * d[.ddd]e+XX / e-XX with at least two exponent digits; "0.0", "-0.0", "inf",
+ * "-inf"; a NaN of either sign is "nan", or with nan_empty != 0 an empty field
+ * (pandas' na_rep).  Every float32 and every float64 is formatted, subnormals
+ * included.
+ * d_row_off[r] = the byte offset of row r's line, d_row_off[n_rows] the total.
+ * d_status[0, 4) = code, bytes needed, row, column:
+ *   0 ok (d_status[1] = the total)
+ *   1 the text is longer than cap_bytes: d_status[1] is the size needed,
+ *     d_row_off is still complete, the contents of d_text are unspecified
+ *     (within its bounds)
+ *   2 d_row_prefix[r] >= n_prefixes, or d_prefix_off is not non-decreasing:
+ *     d_status[2] as for kf_format_kf_rows16; nothing is formatted,
+ *     d_row_off[n_rows] = 0
+ *   3 reserved for a value that cannot be formatted; no value is refused
+ * A line is at most prefix + 1 + 25 * ncols + 1 bytes: callers size cap_bytes by
+ * that, or call twice.  Memory safety, for any input whatever: nothing is
+ * written outside d_text[0, cap_bytes), d_row_off[0, n_rows], d_status[0, 4) and
+ * d_scratch; nothing is read outside d_vals[0, n_rows * ncols), d_prefix_off[0,
+ * n_prefixes], the prefix bytes of a call that is not refused, and
+ * d_row_prefix[0, n_rows).
+ * KF_EINVAL, before any HIP call, for val_bytes other than 4 and 8, a mode that
+ * val_bytes does not have, ncols == 0, sep outside 1..255, eol_len other than 1
+ * and 2, n_rows >= 2^31, cap_bytes >= 2^32 (the caller cuts rows into calls),
+ * n_prefixes < 0, n_rows * ncols >= 2^34 (a launch has fewer than 2^32 threads), a null pointer with n_rows > 0
+ * (d_row_off and d_status always), or a misaligned pointer (val_bytes for d_vals,
+ * 4 for d_row_prefix, 8 for d_prefix_off, d_row_off, d_status and d_scratch;
+ * d_text and d_prefix_bytes need none); KF_ERANGE if scratch_bytes is below
+ * kf_format_float_scratch_bytes, which is the table of powers of ten (9,872
+ * bytes) + 16 + 8 per row + 8 per kf_format_float_tile() = 1,024 cells + 16
+ * per cell (every cell's decimal, kept between the two walks) and does not
+ * decrease when an argument grows.  n_rows == 0 is valid: d_row_off[0] = 0,
+ * status 0.
+ * Five launches and the copy of the table: the prefix table is checked, a
+ * thread per row stores its prefix's length, then the flat cell array is walked
+ * twice in tiles of 1,024 cells (4 per thread, whatever ncols is): the text
+ * length of every tile, and -- after one workgroup scanned those -- the text,
+ * staged in LDS and stored as aligned 16-byte lines with byte stores at a
+ * tile's ragged ends.  The first walk computes a cell's digits and keeps them
+ * in the scratch, the second reads them back (measured against computing them
+ * twice: DESIGN.md section 7).  Asynchronous on `stream`, no allocation, no memset, no
+ * host synchronisation, no workgroup waits for another.
+ * kf_format_float_host: the same inline code on the host for n values: slot i
+ * of out (24 bytes, zero padded) and len[i]; kf_shortest_decimal_host: the
+ * decimal behind the text, w[i] * 10^q[i] (w == 0 unless finite and non-zero)
+ * and cls[i] = class (0 finite, 1 zero, 2 inf, 3 nan) | sign << 7.  The CPU tests
+ * call them, as they call kf_decimal_to_double for the parser. */
+#define KF_FLOAT_SHORTEST 0
+#define KF_FLOAT_WIDENED 1
+int kf_format_float_tile(void);
+uint64_t kf_format_float_scratch_bytes(uint64_t n_rows, uint64_t ncols);
+int kf_format_float_rows(const void* d_vals, int val_bytes, uint64_t n_rows, uint64_t ncols, int mode,
+                         uint32_t sep, uint32_t eol, int eol_len, int nan_empty,
+                         const uint8_t* d_prefix_bytes, const uint64_t* d_prefix_off, int32_t n_prefixes,
+                         const uint32_t* d_row_prefix,
+                         uint8_t* d_text, uint64_t cap_bytes, uint64_t* d_row_off, uint64_t* d_status,
+                         void* d_scratch, uint64_t scratch_bytes, void* stream);
+int kf_format_float_host(const void* vals, int val_bytes, int mode, int nan_empty, uint64_t n,
+                         uint8_t* out, uint8_t* len);
+int kf_shortest_decimal_host(const void* vals, int val_bytes, int mode, uint64_t n,
+                             uint64_t* w, int32_t* q, uint8_t* cls);
+
+/* ---- query's distances (kf2vec/query.py:169-176): out[i, j] for x[Q x D] and
+ * y[B x D], float32, contiguous, is exactly
+ *   s = 0; for d ascending: t = x_d - y_d, s = s + t * t; r = sqrt(s); v = r * r;
+ *   out = v < 1e-6f ? 0 : v
+ * with every operation rounded to float32 and none contracted into an fma: the
+ * direct form of torch.cdist(compute_mode='donot_use_mm_for_euclid_dist'),
+ * squared and cut as the reference does, which keeps the digits of small
+ * distances that the matmul form cancels.  The order over d is fixed, so the
+ * result does not depend on how Q and B are cut into tiles or into calls.
+ * Tiles of kf_sq_distances_tile() = 64 rows of x and of y go through LDS, read
+ * from HBM once per tile pair.  No scratch; asynchronous on `stream`.
+ * KF_EINVAL, before any HIP call, for D == 0, a null pointer that the sizes
+ * need, a pointer not aligned to 4 bytes, or 2^24 tiles or more (a launch has
+ * fewer than 2^32 threads: the caller cuts Q or B).  Q == 0 or B ==
+ * 0 is valid and writes nothing. */
+int kf_sq_distances_tile(void);
+int kf_sq_distances(const float* d_x, uint64_t Q, const float* d_y, uint64_t B, uint64_t D,
+                    float* d_out, void* stream);
+
 /* Hash of the sources this library was built from (csrc/ + this header, as
  * kf2vecfsw_amd/build.py computes it): 16 hex digits, with a "+<tag>" suffix for
  * profiling builds.  The Python binding refuses a library whose id differs from

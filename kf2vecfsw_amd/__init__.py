@@ -8,7 +8,10 @@ Layout:
   counter.py          batch packing + KmerCounter (device counting)
   main.py             `get_frequencies` CLI mirror
   features.py         a get_frequencies `.kf` directory as the trainers' float64 matrix
-  tables.py           distance matrices and embedding tables (tab-separated floats) on the device
+  tables.py           distance matrices and embedding tables (tab-separated floats) on the device: read
+                      (kf_parse_tsv_floats) and written (kf_format_float_rows, write_float_table)
+  query.py            `query`: distances to a clade's backbone (kf_sq_distances) and embeddings, written
+                      as text formatted on the device
 """
 __all__ = ["__version__"]
 __version__ = "0.1.0"

@@ -24,6 +24,7 @@ KF_MAX_K = 12
 KF_SPARSE_MAX_K = 31
 KF_ACCUMULATE = 1
 KF_FMT_AUTO, KF_FMT_FASTA, KF_FMT_FASTQ = 0, 1, 2
+KF_FLOAT_SHORTEST, KF_FLOAT_WIDENED = 0, 1
 
 # every symbol declared in include/kf2vec_gpu.h: (restype, argtypes)
 _u64, _u32, _i32, _i64, _int = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int
@@ -81,6 +82,14 @@ SIGNATURES = {
     "kf_format_kf_scratch_bytes": (_u64, [_u64, _u64]),
     "kf_format_kf_rows16": (_int, [_vp, _u64, _u64, _vp, _vp, _i32, _vp, _vp, _u32, _int, _vp, _u64, _vp, _vp, _vp, _u64,
                                    _vp]),
+    "kf_format_float_tile": (_int, []),
+    "kf_format_float_scratch_bytes": (_u64, [_u64, _u64]),
+    "kf_format_float_rows": (_int, [_vp, _int, _u64, _u64, _int, _u32, _u32, _int, _int, _vp, _vp, _i32, _vp, _vp, _u64,
+                                    _vp, _vp, _vp, _u64, _vp]),
+    "kf_format_float_host": (_int, [_vp, _int, _int, _int, _u64, _vp, _vp]),
+    "kf_shortest_decimal_host": (_int, [_vp, _int, _int, _u64, _vp, _vp, _vp]),
+    "kf_sq_distances_tile": (_int, []),
+    "kf_sq_distances": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp]),
     "kf_write_text_segments": (_int, [_i32, ctypes.POINTER(_cp), _vp, _vp, _vp, _int]),
 }
 

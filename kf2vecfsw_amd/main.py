@@ -24,6 +24,8 @@ from . import _native as N
 __version__ = "kf2vec 0.1.3 (kf2vecfsw_amd MI355X)"
 
 default_k_len = 7          # main.py:80
+default_seed = 28          # main.py:97
+default_block_sz = 4000    # main.py:98
 min_k_len = 2              # main.py:81
 max_k_len = 31             # main.py:82
 supported_k = range(3, 12)  # rule-generated vocab (reference ships 3..9; 10 is a missing blob)
@@ -1361,6 +1363,13 @@ def get_chunks(args) -> None:
         CH.trace.clear()
 
 
+def query(args) -> None:
+    """`query`: distances to the backbone and embeddings of the queries, computed
+    and written as text on the device (query.query_func; kf2vec/main.py:535-553)."""
+    from . import query as Q
+    Q.query(args)
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="K-mer frequency to distance\n{}".format(__version__),
                                      formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -1370,7 +1379,8 @@ def build_parser() -> argparse.ArgumentParser:
                                             "FASTA files\n"
                                             "get_frequencies          Extract k-mer frequency from a reference "
                                             "genome-skims or assemblies\n"
-                                            "get_chunks               Extract chunks from reference assemblies\n")
+                                            "get_chunks               Extract chunks from reference assemblies\n"
+                                            "query                    Query models\n")
     pf = sub.add_parser("get_frequencies", description="Process a library of reference genome-skims or assemblies")
     pf.add_argument("-input_dir", help="Directory of input genomes or assemblies "
                                        "(dir of .fastq/.fq/.fa/.fna/.fasta files)")
@@ -1418,6 +1428,22 @@ def build_parser() -> argparse.ArgumentParser:
     pc.add_argument("-batch_gb", type=float, default=1.0, help="Window bytes per device batch (GiB)")
     pc.add_argument("-device", default=None, help="torch device (default: cuda)")
     pc.set_defaults(func=get_chunks)
+
+    pq = sub.add_parser("query", description="Query models")
+    pq.add_argument("-input_dir", help="Directory of input k-mer frequencies for assemblies or reads "
+                                       "(dir of .kf files for queries)")
+    pq.add_argument("-model", help="Directory of models and embeddings (dir of model_subtree_INDEX.ckpt and "
+                                   "embeddings_subtree_INDEX.csv files for backbone)")
+    pq.add_argument("-classes", help="Path to classification file with subtrees information obtained from classify "
+                                     "command (classes.out file)")
+    pq.add_argument("-block", type=int, default=default_block_sz,
+                    help="Block size for file processing. Default: {}".format(default_block_sz))
+    pq.add_argument("-seed", type=int, default=default_seed, help="Random seed. Default: {}".format(default_seed))
+    pq.add_argument("-remap", help='Remap file with alternative output names ("label" and "new_label" columns in '
+                                   ".tsv format)")
+    pq.add_argument("-o", help="Output path")
+    pq.add_argument("-device", default=None, help="torch device (default: cuda)")
+    pq.set_defaults(func=query)
     return parser
 
 

@@ -421,3 +421,314 @@ def backbone_embeddings(path: str, device="cuda") -> FloatTable:
     on the device, every value the correctly rounded float64 of its decimal
     rounded once more to float32, and the names as text in file order."""
     return table_from_tsv(path, device, header=False, dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------
+# float tables written out: the text formatted on the device (kf_format_float_rows)
+# ---------------------------------------------------------------------------
+KF_FLOAT_SHORTEST, KF_FLOAT_WIDENED = N.KF_FLOAT_SHORTEST, N.KF_FLOAT_WIDENED
+FLOAT_TEXT_MAX = 24                  # bytes of one float's text at most
+
+
+def float_row_bound(ncols: int, max_label_len: int, eol_len: int = 2) -> int:
+    """Bytes that no line of format_float_rows exceeds: the label and its
+    separator, 24 bytes and a separator per column, and the end of line."""
+    return int(max_label_len) + 1 + (FLOAT_TEXT_MAX + 1) * int(ncols) + int(eol_len)
+
+
+def quote_label(label, sep: str = "\t", eol: str = "\r\n") -> bytes:
+    """A label as csv.writer(delimiter=sep, lineterminator=eol) writes it as the
+    first of several fields (the csv module's own QUOTE_MINIMAL rules: quoted if it
+    holds the separator, a quote or a line break); what is not text goes through
+    str() as the writer does, None is the empty field."""
+    import csv
+    import io
+    buf = io.StringIO(newline="")
+    csv.writer(buf, delimiter=sep, lineterminator=eol).writerow([label, "x"])
+    out = buf.getvalue()
+    return out[: len(out) - len(sep) - 1 - len(eol)].encode(errors="surrogateescape")
+
+
+def _float_form(values, mode: int) -> int:
+    size = values.element_size() if isinstance(values, torch.Tensor) else values.dtype.itemsize
+    if (size, mode) not in ((8, KF_FLOAT_SHORTEST), (4, KF_FLOAT_SHORTEST), (4, KF_FLOAT_WIDENED)):
+        raise ValueError("mode {} with {}-byte values: KF_FLOAT_SHORTEST, or KF_FLOAT_WIDENED for float32".format(
+            mode, size))
+    return size
+
+
+def _encode_labels(labels, n: int):
+    """(the labels as bytes or None, the longest one's length)."""
+    if labels is None:
+        return None, 0
+    enc = [x if isinstance(x, (bytes, bytearray)) else str(x).encode(errors="surrogateescape") for x in labels]
+    if len(enc) != n:
+        raise ValueError("{} labels for {} rows".format(len(enc), n))
+    return enc, max([len(x) for x in enc], default=0)
+
+
+def format_float_call(values: torch.Tensor, enc, mode: int, sep: str = "\t", eol: str = "\r\n",
+                      nan_empty: bool = False, cap_bytes: int | None = None, stream: int | None = None):
+    """Enqueue ONE kf_format_float_rows: values [n, ncols] (float32 or float64,
+    contiguous, on the device) with row r's label enc[r] (bytes, already quoted;
+    enc=None: no label and no leading separator).  cap_bytes: the size of the
+    text buffer, by default n times float_row_bound, which must stay below 2^32.
+    Returns (text uint8 [cap_bytes], row_off int64 [n + 1], status int64 [4]) on
+    the device; nothing waits."""
+    assert values.dim() == 2 and values.is_contiguous() and values.dtype in (torch.float32, torch.float64)
+    _float_form(values, mode)
+    dev = values.device
+    n, ncols = int(values.shape[0]), int(values.shape[1])
+    sep_b, eol_b = sep.encode(), eol.encode()
+    assert len(sep_b) == 1 and len(eol_b) in (1, 2)
+    if enc is None:
+        pre, rpre = [b""], np.zeros(n, dtype=np.int32)
+    else:
+        pre, rpre = enc, np.arange(n, dtype=np.int32)
+    pre_off = np.zeros(len(pre) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in pre], out=pre_off[1:])
+    blob = np.frombuffer(b"".join(pre) + b"\0", dtype=np.uint8)   # never empty: an address for no prefix bytes
+    d_pre = torch.from_numpy(blob.copy()).to(dev, non_blocking=True)
+    d_pre_off = torch.from_numpy(pre_off).to(dev, non_blocking=True)
+    d_rpre = torch.from_numpy(rpre).to(dev, non_blocking=True)
+    if cap_bytes is None:
+        cap_bytes = n * float_row_bound(ncols, max([len(x) for x in pre], default=0), len(eol_b))
+    cap_bytes = int(cap_bytes)
+    text = torch.empty(max(cap_bytes, 1), dtype=torch.uint8, device=dev)
+    row_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(4, dtype=torch.int64, device=dev)
+    need = int(N.lib().kf_format_float_scratch_bytes(n, ncols))
+    scratch = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    s = C._stream_ptr(dev) if stream is None else stream
+    with torch.cuda.device(dev):
+        N.check(N.lib().kf_format_float_rows(
+            values.data_ptr(), values.element_size(), n, ncols, int(mode), sep_b[0],
+            eol_b[0] | (eol_b[1] << 8 if len(eol_b) == 2 else 0), len(eol_b), int(bool(nan_empty)), d_pre.data_ptr(),
+            d_pre_off.data_ptr(), len(pre), d_rpre.data_ptr(), text.data_ptr(), cap_bytes, row_off.data_ptr(),
+            status.data_ptr(), scratch.data_ptr(), 8 * scratch.numel(), s), "kf_format_float_rows")
+    if stream is not None:   # the tables and the scratch are the caller's stream's until the call is done
+        for t in (d_pre, d_pre_off, d_rpre, scratch):
+            t.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+    return text[:cap_bytes], row_off, status
+
+
+def float_status_check(code: int, need: int, row: int, col: int = 0, cap_bytes: int | None = None) -> None:
+    """Raise what kf_format_float_rows' status words say (nothing for code 0)."""
+    if code == 1:
+        raise N.NativeError("kf_format_float_rows: the text needs {} bytes{} (status 1)".format(
+            need, "" if cap_bytes is None else ", {} allowed for".format(cap_bytes)))
+    if code == 2:
+        raise ValueError("row {}: a row's prefix is out of range, or the prefix offsets decrease "
+                         "(kf_format_float_rows status 2)".format(row))
+    if code != 0:
+        raise ValueError("row {}, column {}: a value that cannot be formatted (kf_format_float_rows status {})".format(
+            row, col, code))
+
+
+def format_float_rows(values: torch.Tensor, labels=None, mode: int = KF_FLOAT_SHORTEST, sep: str = "\t",
+                      eol: str = "\r\n", nan_empty: bool = False):
+    """The table `values` [n, ncols] (float32 or float64 on the device) as text,
+    formatted there: row r is  label_r sep f sep ... f eol  (labels=None: no label
+    and no leading separator; labels are written as given: quote_label quotes).
+    mode KF_FLOAT_SHORTEST: a float64 as repr(float), a float32 as
+    str(np.float32); KF_FLOAT_WIDENED (float32): repr of the value as a double,
+    which is what .tolist() and csv.writer write.  nan_empty: NaN is an empty
+    field (pandas) instead of "nan" (csv.writer).  format_float_rows_host states
+    it on the host.  The rows are cut into calls whose text bound stays below
+    4 GiB.  Returns (text uint8 on the device, row_off int64 numpy [n + 1])."""
+    values = values.contiguous()
+    n, ncols = int(values.shape[0]), int(values.shape[1])
+    enc, longest = _encode_labels(labels, n)
+    bound = float_row_bound(ncols, longest, len(eol.encode()))
+    if bound > C.KF_FORMAT_MAX_CAP:
+        raise ValueError("a row of {} columns may need {} bytes of text: 4 GiB or more".format(ncols, bound))
+    per = max(1, C.KF_FORMAT_MAX_CAP // bound)
+    parts, offs, base = [], [np.zeros(1, dtype=np.int64)], 0
+    for r0 in range(0, max(n, 1), per):
+        r1 = min(n, r0 + per)
+        text, row_off, status = format_float_call(values[r0:r1], None if enc is None else enc[r0:r1], mode, sep, eol,
+                                                  nan_empty)
+        both = torch.cat([status, row_off]).cpu().numpy()
+        float_status_check(int(both[0]), int(both[1]), r0 + int(both[2]), int(both[3]), int(text.numel()))
+        off = both[4:]
+        parts.append(text[: int(off[-1])])
+        offs.append(off[1:] + base)
+        base += int(off[-1])
+    text = parts[0] if len(parts) == 1 else torch.cat(parts)
+    return text, np.concatenate(offs)
+
+
+def float_text_host(values, mode: int = KF_FLOAT_SHORTEST, nan_empty: bool = False) -> list:
+    """Every value's text as Python and numpy print it: repr(float(v)) for a
+    float64 and for a float32 in KF_FLOAT_WIDENED mode, str(np.float32(v)) for a
+    float32 in KF_FLOAT_SHORTEST mode; NaN "nan" or, with nan_empty, nothing."""
+    a = np.ascontiguousarray(values.cpu().numpy() if isinstance(values, torch.Tensor) else values)
+    size = _float_form(a, mode)
+    flat = a.reshape(-1)
+    if size == 4 and mode == KF_FLOAT_SHORTEST:
+        out = [str(v) for v in flat]
+    else:
+        with np.errstate(invalid="ignore"):    # a signalling NaN widens to a quiet one
+            out = [repr(v) for v in flat.astype(np.float64).tolist()]
+    if nan_empty:
+        for i in np.flatnonzero(np.isnan(flat)):
+            out[i] = ""
+    return out
+
+
+def format_float_rows_host(values, labels=None, mode: int = KF_FLOAT_SHORTEST, sep: str = "\t", eol: str = "\r\n",
+                           nan_empty: bool = False):
+    """The host statement of format_float_rows: (the text as bytes, row_off int64
+    [n + 1]), built from Python's repr and numpy's str (float_text_host).  The
+    tests compare the kernel with it; no product path calls it."""
+    a = values.cpu().numpy() if isinstance(values, torch.Tensor) else np.asarray(values)
+    n, ncols = a.shape
+    enc, _ = _encode_labels(labels, n)
+    cells = float_text_host(a, mode, nan_empty)
+    sep_b, eol_b = sep.encode(), eol.encode()
+    lines, off = [], np.zeros(n + 1, dtype=np.int64)
+    for r in range(n):
+        body = sep_b.join(x.encode() for x in cells[r * ncols: (r + 1) * ncols])
+        line = (enc[r] + sep_b if enc is not None and enc[r] else b"") + body + eol_b
+        lines.append(line)
+        off[r + 1] = off[r] + len(line)
+    return b"".join(lines), off
+
+
+def header_line(header, sep: str = "\t", eol: str = "\r\n") -> bytes:
+    """A header's cells as csv.writer(delimiter=sep, lineterminator=eol) writes the row."""
+    import csv
+    import io
+    buf = io.StringIO(newline="")
+    csv.writer(buf, delimiter=sep, lineterminator=eol).writerow(list(header))
+    return buf.getvalue().encode(errors="surrogateescape")
+
+
+class FloatTableWriter:
+    """Float tables formatted on the device and written by a thread of its own, so
+    a table's copy to the host and its file write overlap the device work that
+    the caller enqueues next (query: the next block).  write() enqueues the
+    format calls on the current stream and returns; the writer thread waits for
+    each call's row offsets, copies the text it names through a pinned buffer on
+    a second stream and hands it to kf_write_text_segments.  At most max_pending
+    tables are in flight: write() waits for the oldest before it enqueues
+    another, so the text held on the device and in pinned memory does not grow
+    with the number of blocks when the disk is slower than the device.  close() (or leaving
+    the with block) waits for every write and raises what one of them raised."""
+
+    def __init__(self, device, threads: int = 1):
+        self.device = torch.device(device)
+        self.threads = max(1, int(threads))
+        self.d2h = torch.cuda.Stream(self.device)
+        self.pool = ThreadPoolExecutor(max_workers=1)
+        self.pending = []
+        self.max_pending = 2             # tables in flight: each holds its text on the device and a pinned copy
+        self.times = {"copy_back": 0.0, "file_write": 0.0}
+
+    def write(self, path: str, labels, values: torch.Tensor, header=None, mode: int = KF_FLOAT_SHORTEST,
+              sep: str = "\t", eol: str = "\r\n", nan_empty: bool = False, append: bool = False) -> None:
+        while len(self.pending) >= self.max_pending:   # a slow disk holds the caller back, not memory
+            self.pending.pop(0).result()
+        values = values.contiguous()
+        n, ncols = int(values.shape[0]), int(values.shape[1])
+        enc = None if labels is None else [quote_label(x, sep, eol) for x in labels]
+        enc, longest = _encode_labels(enc, n)
+        head = header_line(header, sep, eol) if header is not None else b""
+        bound = float_row_bound(ncols, longest, len(eol.encode()))
+        if bound > C.KF_FORMAT_MAX_CAP:
+            raise ValueError("a row of {} columns may need {} bytes of text: 4 GiB or more".format(ncols, bound))
+        per = max(1, C.KF_FORMAT_MAX_CAP // bound)
+        stream = torch.cuda.current_stream(self.device)
+        calls = []
+        for r0 in range(0, n, per):
+            r1 = min(n, r0 + per)
+            text, row_off, status = format_float_call(values[r0:r1], None if enc is None else enc[r0:r1], mode, sep,
+                                                      eol, nan_empty)
+            done = torch.cuda.Event()
+            done.record(stream)
+            self.d2h.wait_event(done)
+            small = torch.empty(8, dtype=torch.int64, pin_memory=True)
+            with torch.cuda.stream(self.d2h):
+                small[:4].copy_(status, non_blocking=True)
+                small[4:5].copy_(row_off[-1:], non_blocking=True)
+                for t in (text, row_off, status, values):
+                    t.record_stream(self.d2h)
+                ev = torch.cuda.Event()
+                ev.record(self.d2h)
+            calls.append((r0, text, small, ev))
+        self.pending.append(self.pool.submit(self._finish, path, head, calls, append))
+
+    def _finish(self, path: str, head: bytes, calls, append: bool) -> None:
+        import ctypes
+        import time
+        lib = N.lib()
+        first = True
+        if not calls:
+            calls = [(0, None, None, None)]
+        with torch.cuda.device(self.device):
+            for r0, text, small, ev in calls:
+                t0 = time.perf_counter()
+                total = 0
+                if text is not None:
+                    ev.synchronize()
+                    h = small.numpy()
+                    float_status_check(int(h[0]), int(h[1]), r0 + int(h[2]), int(h[3]), int(text.numel()))
+                    total = int(h[4])
+                lead = head if first else b""
+                host = torch.empty(max(len(lead) + total, 1), dtype=torch.uint8, pin_memory=True)
+                if lead:
+                    host.numpy()[: len(lead)] = np.frombuffer(lead, dtype=np.uint8)
+                if total:
+                    with torch.cuda.stream(self.d2h):
+                        host[len(lead): len(lead) + total].copy_(text[:total], non_blocking=True)
+                    self.d2h.synchronize()
+                t1 = time.perf_counter()
+                cp = (ctypes.c_char_p * 1)(os.fsencode(path))
+                ap = np.asarray([1 if (append or not first) else 0], dtype=np.uint8)
+                so = np.asarray([0, len(lead) + total], dtype=np.uint64)
+                N.check(lib.kf_write_text_segments(1, cp, ap.ctypes.data, so.ctypes.data, host.data_ptr(),
+                                                   self.threads), "kf_write_text_segments")
+                first = False
+                self.times["copy_back"] += t1 - t0
+                self.times["file_write"] += time.perf_counter() - t1
+
+    def drain(self) -> None:
+        while self.pending:
+            self.pending.pop(0).result()
+
+    def close(self) -> None:
+        try:
+            self.drain()
+        finally:
+            self.pool.shutdown()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def write_float_table(path: str, labels, values: torch.Tensor, header=None, mode: int = KF_FLOAT_SHORTEST,
+                      sep: str = "\t", eol: str = "\r\n", nan_empty: bool = False, append: bool = False,
+                      threads: int = 1) -> None:
+    """Write the table `values` [n, ncols] (float32 or float64 on the device) to
+    `path` as text formatted on the device (format_float_rows): an optional
+    header row, then a line per row with its label first (labels=None: none).
+    Header cells and labels are quoted on the host by the csv module's own rules
+    (quote_label); the text crosses to the host through a pinned buffer and
+    kf_write_text_segments writes it.  append: the file's end is where writing
+    starts, else the file is truncated.
+    The reference's tables: query's two files are mode=KF_FLOAT_WIDENED with the
+    defaults ('\\t', '\\r\\n', "nan"); DataFrame.to_csv(sep='\\t') of a float32 frame
+    is mode=KF_FLOAT_SHORTEST, eol='\\n', nan_empty=True; a `.di_mtrx` is a float64
+    tensor in the same form.
+    Reading back: float64 text and KF_FLOAT_WIDENED text return the same bits
+    through this project's parsers.  The float32 form of KF_FLOAT_SHORTEST is the
+    shortest decimal for a reader that rounds once; the parsers (like strtod and
+    a cast, and like numpy) go through the nearest double, and for one float32
+    and its negative, 0x15ae43fd printed 7.038531e-26, that lands one unit off
+    (profiles/r20/float32_exhaustive.json)."""
+    with FloatTableWriter(values.device, threads) as w:
+        w.write(path, labels, values, header, mode, sep, eol, nan_empty, append)
