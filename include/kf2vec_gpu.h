@@ -864,7 +864,10 @@ int kf_write_text_segments(int32_t n_seg, const char* const* paths, const uint8_
 /* ---- get_chunks device pre-pass (replaces seqtk seq -l 0 | awk N-collapse |
  * seqkit seq -g -m, main.py:726-760).  d_seq holds n_rec sorted, disjoint
  * [start, end) byte ranges of record sequences (the bytes between a header's
- * '\n' and the next header).  Writes each record's processed sequence --
+ * '\n' and the next header); any such ranges do, cut mid-line or touching, but
+ * every one must lie inside [0, len]: the bounds are clamped to len, the byte
+ * rule is not (it reads d_bytes[j + 1] wherever j + 1 is below the range's
+ * end).  Writes each record's processed sequence --
  * newlines and line-end '\r' dropped, the gap letters "- \t." dropped, runs of
  * N / n / '|' (awk runs before seqkit: gap letters split a run) collapsed to
  * one 'N' -- back to back into d_out (>= len bytes) and its [start, end) into

@@ -549,6 +549,33 @@ class ChunkPipeline:
         self.copier.shutdown()
 
 
+def compact_records_host(data, se) -> tuple[bytes, np.ndarray]:
+    """The host statement of kf_chunk_compact (include/kf2vec_gpu.h has the
+    contract): (out, out_se uint64 [2n]) for the n sorted, disjoint ranges
+    se = [a0, b0, a1, b1, ...] of `data`.  Range r is seqtk -> awk -> seqkit
+    applied to data[a:b]: split at '\\n', one trailing '\\r' dropped from every
+    piece (the last one included), the pieces joined, [Nn|]+ -> N, then the gap
+    letters "- \\t." deleted.  `out` is the results back to back and
+    out_se[2r], out_se[2r+1] the running offsets.  Regular expressions and no
+    look-back, so it shares nothing with the kernel's per-byte rule.  Only
+    tests call it; no product path does."""
+    import re
+    data = bytes(data) if isinstance(data, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(data, dtype=np.uint8).tobytes()
+    se = np.asarray(se, dtype=np.uint64).reshape(-1)
+    nrun, gaps = re.compile(rb"[Nn|]+"), re.compile(rb"[- \t.]")
+    parts, out_se, pos = [], np.zeros(se.size, dtype=np.uint64), 0
+    for r in range(se.size // 2):
+        a, b = int(se[2 * r]), int(se[2 * r + 1])
+        seq = b"".join(p[:-1] if p.endswith(b"\r") else p for p in data[a:b].split(b"\n"))
+        seq = gaps.sub(b"", nrun.sub(b"N", seq))
+        parts.append(seq)
+        out_se[2 * r] = pos
+        pos += len(seq)
+        out_se[2 * r + 1] = pos
+    return b"".join(parts), out_se
+
+
 # ---------------------------------------------------------------------------
 # in-memory hand-off to the chunk trainer (kf_chunk_features)
 # ---------------------------------------------------------------------------

@@ -107,3 +107,44 @@ def model_count(data: bytes, excl: np.ndarray, base: int, k: int, rank_std: np.n
             counts[rank_std[min(fw, rc)]] += 1
             total += 1
     return counts, total
+
+
+def chunk_genome(rng: np.random.Generator, n_contigs: int) -> bytes:
+    """Multi-contig FASTA that exercises get_chunks' pre-pass: N / n / '|' runs
+    (collapsed), gap letters "- \\t." (dropped; they split N runs), CRLF lines,
+    blank lines, lowercase, contigs around the 10 kbp threshold."""
+    out = []
+    for c in range(n_contigs):
+        L = int(rng.choice([3000, 9999, 10000, 10001, 15000, 24000, 61000]))
+        seq = random_seq(rng, L, lower=0.02).copy()
+        for _ in range(int(rng.integers(0, 12))):
+            a = int(rng.integers(0, max(1, L - 300)))
+            seq[a: a + int(rng.integers(1, 300))] = np.frombuffer(b"NNnn|N", np.uint8)[rng.integers(0, 6)]
+        for _ in range(int(rng.integers(0, 20))):
+            seq[int(rng.integers(0, L))] = np.frombuffer(b"- \t.", np.uint8)[rng.integers(0, 4)]
+        body = wrap(seq, int(rng.choice([60, 70, 80, 1000])), crlf=bool(rng.random() < 0.3))
+        if rng.random() < 0.2:
+            body = body.replace(b"\n", b"\n\n", 3)
+        if rng.random() < 0.2:
+            out.append(b">empty%d\n" % c)            # an empty record: its header merges with the next
+        out.append(b">ctg%d some description\n" % c + body)
+    return b"".join(out)
+
+
+def header_pairs(data, off) -> list[int]:
+    """The pairs kf_index_fasta writes for the genomes [off[g], off[g + 1]) of
+    `data`, stated line by line: a '>' at a genome's first byte or right after a
+    '\\n' starts a header, which ends at the first '\\n' at or after it inside the
+    genome, or else at the genome's end.  A flat sorted [s0, e0, s1, e1, ...]."""
+    data = bytes(data) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data, np.uint8).tobytes()
+    off = [int(x) for x in off]
+    offa = np.asarray(off, dtype=np.int64)
+    out: list[int] = []
+    for i in np.flatnonzero(np.frombuffer(data, np.uint8) == ord(">")).tolist():
+        if not off[0] <= i < off[-1]:
+            continue
+        g = int(np.searchsorted(offa, i, side="right")) - 1    # the genome of byte i
+        if i == off[g] or data[i - 1] == 10:
+            e = data.find(b"\n", i, off[g + 1])
+            out += [i, off[g + 1] if e < 0 else e]
+    return out

@@ -143,3 +143,102 @@ def test_device_index_scan_carry_past_1024_blocks(torch_dev):
                            for i in range(2)])
     nl = d == 10
     assert np.array_equal(excluded_mask(pairs, n) & ~nl, excluded_mask(host, n) & ~nl)
+
+
+# ------------------------------------------------------------------ exact pairs
+def device_pairs(dev, data: np.ndarray, off) -> list:
+    """counter.index_on_device on a buffer of exactly off[-1] bytes: the pairs as a list."""
+    import torch
+    from kf2vecfsw_amd import counter as C
+    off = np.asarray(off, dtype=np.int64)
+    n = int(off[-1])
+    assert data.size == n
+    d = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+    with torch.cuda.device(dev):
+        excl, m = C.index_on_device(d, torch.from_numpy(off).to(dev), off.size - 1, n)
+    pairs = excl.cpu().numpy().tolist()
+    assert len(pairs) == 2 * m
+    return pairs
+
+
+def strings6() -> np.ndarray:
+    """All 4^6 = 4,096 strings of length 6 over ">A\\n\\r", [4096, 6]."""
+    x = np.arange(4 ** 6)
+    digits = np.stack([(x // 4 ** (5 - p)) % 4 for p in range(6)], axis=1)
+    return np.frombuffer(b">A\n\r", np.uint8)[digits]
+
+
+@pytest.mark.parametrize("layout", ["one_genome", "genome_per_string", "genome_per_3_strings"])
+def test_device_index_exact_pairs_every_6_byte_string(torch_dev, layout):
+    """The pairs themselves (not the mask of excluded bytes) equal gen.header_pairs
+    on every string of length 6 over ">A\\n\\r", back to back after 0..15 bytes
+    'A' (every phase of a thread's 16 bytes): a pair that ends a byte late on its
+    '\\n', or a header split in two, fails here.  With a genome boundary at every
+    string's start (unaligned offsets: a '>' whose predecessor is not '\\n' is a
+    header only if the binary search finds a genome start there) and at every
+    third string."""
+    body = strings6().reshape(-1)
+    every = {"one_genome": 4096, "genome_per_string": 1, "genome_per_3_strings": 3}[layout]
+    n_pairs = 0
+    for pad in range(16):
+        data = np.concatenate([np.full(pad, ord("A"), np.uint8), body])
+        off = sorted({0, data.size} | ({pad + 6 * s for s in range(0, 4096, every)} if every < 4096 else set()))
+        exp = gen.header_pairs(data, off)
+        assert device_pairs(torch_dev, data, off) == exp, (layout, pad)
+        n_pairs += len(exp) // 2
+    assert n_pairs > 16 * 1000, n_pairs
+
+
+INDEX_MOTIFS = [b">", b">\n", b"\n>", b"A>", b"\r>", b">>\n>", b"\n>hd"]
+
+
+@pytest.mark.parametrize("boundary", [False, True])
+def test_device_index_exact_pairs_across_tile_edges(torch_dev, boundary):
+    """'>' alone, before and after a '\\n', after 'A' and '\\r', doubled, and a header
+    that runs to its genome's end, with each byte in turn first after a thread,
+    wave and workgroup edge (16, 1024, 4096, 8192); with a genome boundary exactly
+    on the edge, and with none."""
+    places = [(E, m, k) for E in (16, 1024, 4096, 8192) for m in INDEX_MOTIFS for k in range(len(m) + 1)]
+    data = np.full((len(places) + 2) * 3 * 4096, ord("A"), np.uint8)
+    data[97::101] = 10
+    cuts = {0, data.size}
+    for c, (E, m, k) in enumerate(places):
+        edge = (c + 1) * 3 * 4096 + E                 # the copies are three workgroup spans apart
+        data[edge - 8: edge + 8] = ord("A")
+        data[edge - k: edge - k + len(m)] = np.frombuffer(m, np.uint8)
+        if boundary:
+            cuts.add(edge)
+    off = sorted(cuts)
+    exp = gen.header_pairs(data, off)
+    assert len(exp) // 2 >= len(places) // 2
+    assert device_pairs(torch_dev, data, off) == exp
+
+
+def test_device_index_cap_pairs(torch_dev):
+    """kf_index_fasta with a table of exactly m pairs, of m - 1 (the count is still
+    m, the first m - 1 pairs are right and nothing is written from entry 2 (m - 1)
+    on) and of none (a null table: only the count)."""
+    import torch
+    from kf2vecfsw_amd import _native as N
+    data = np.concatenate([np.full(5, ord("A"), np.uint8), strings6().reshape(-1)])
+    off = np.asarray(sorted({0, data.size} | {5 + 18 * s for s in range(1366)}), dtype=np.int64)
+    exp = gen.header_pairs(data, off)
+    m, n = len(exp) // 2, int(data.size)
+    assert m > 1000
+    d = torch.from_numpy(data).to(torch_dev)
+    d_off = torch.from_numpy(off).to(torch_dev)
+    words = (n + 4095) // 4096 + 1
+    scratch = torch.empty(words, dtype=torch.int32, device=torch_dev)
+    mark = -0x5A5A5A5A5A5A5A5B
+    for cap, null_table in ((m, False), (m - 1, False), (0, True)):
+        table = torch.full((2 * m + 8,), mark, dtype=torch.int64, device=torch_dev)
+        count = torch.full((1,), mark, dtype=torch.int64, device=torch_dev)
+        N.check(N.lib().kf_index_fasta(d.data_ptr(), d_off.data_ptr(), off.size - 1, n,
+                                       None if null_table else table.data_ptr(), cap, count.data_ptr(),
+                                       scratch.data_ptr(), words, torch.cuda.current_stream(torch_dev).cuda_stream),
+                "kf_index_fasta")
+        torch.cuda.synchronize()
+        assert int(count.item()) == m, cap
+        got = table.cpu().numpy()
+        assert got[: 2 * cap].tolist() == exp[: 2 * cap], cap
+        assert (got[2 * cap:] == mark).all(), cap

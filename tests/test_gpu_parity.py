@@ -775,28 +775,6 @@ def test_cli_64_bacterial_like_genomes(torch_dev, oracle, tmp_path):
     assert not bad, bad
 
 
-def _chunk_genome(rng, n_contigs):
-    """Multi-contig FASTA that exercises get_chunks' pre-pass: N / n / '|' runs
-    (collapsed), gap letters "- \\t." (dropped; they split N runs), CRLF lines,
-    blank lines, lowercase, contigs around the 10 kbp threshold."""
-    out = []
-    for c in range(n_contigs):
-        L = int(rng.choice([3000, 9999, 10000, 10001, 15000, 24000, 61000]))
-        seq = gen.random_seq(rng, L, lower=0.02).copy()
-        for _ in range(int(rng.integers(0, 12))):
-            a = int(rng.integers(0, max(1, L - 300)))
-            seq[a: a + int(rng.integers(1, 300))] = np.frombuffer(b"NNnn|N", np.uint8)[rng.integers(0, 6)]
-        for _ in range(int(rng.integers(0, 20))):
-            seq[int(rng.integers(0, L))] = np.frombuffer(b"- \t.", np.uint8)[rng.integers(0, 4)]
-        body = gen.wrap(seq, int(rng.choice([60, 70, 80, 1000])), crlf=bool(rng.random() < 0.3))
-        if rng.random() < 0.2:
-            body = body.replace(b"\n", b"\n\n", 3)
-        if rng.random() < 0.2:
-            out.append(b">empty%d\n" % c)            # an empty record: its header merges with the next
-        out.append(b">ctg%d some description\n" % c + body)
-    return b"".join(out)
-
-
 def test_chunk_compact_matches_oracle(torch_dev, oracle):
     """kf_chunk_compact (device linearise + N-run collapse + gap removal) == the
     oracle's restatement of seqtk seq -l 0 | awk gsub | seqkit seq -g, record by
@@ -805,7 +783,7 @@ def test_chunk_compact_matches_oracle(torch_dev, oracle):
     from kf2vecfsw_amd import counter as C
     from kf2vecfsw_amd import _native as N
     rng = np.random.default_rng(4040)
-    datas = [_chunk_genome(rng, int(rng.integers(1, 12))) for _ in range(6)]
+    datas = [gen.chunk_genome(rng, int(rng.integers(1, 12))) for _ in range(6)]
     datas += [b">a\n>b x\n" + gen.wrap(gen.random_seq(rng, 23000), 60) + b">c\n>d\n>e\n" +
               gen.wrap(gen.random_seq(rng, 12000), 80)]                  # empty records (merged headers)
     pipe = CH.ChunkPipeline(counter(7, torch_dev), torch_dev, 16, 2)
@@ -867,7 +845,7 @@ def test_cli_get_chunks_multicontig_vs_oracle(torch_dev, oracle, tmp_path):
     rng = np.random.default_rng(5050)
     inp = tmp_path / "in"
     inp.mkdir()
-    genomes = {f"g{i}": _chunk_genome(rng, int(rng.integers(1, 9))) for i in range(7)}
+    genomes = {f"g{i}": gen.chunk_genome(rng, int(rng.integers(1, 9))) for i in range(7)}
     for name, b in genomes.items():
         (inp / f"{name}.fna").write_bytes(b)
     for batch_gb in ("1", "0.00005"):   # 0.00005 GiB ~ 5 windows: flushes inside and across genomes
@@ -899,13 +877,13 @@ def test_cli_get_chunks_record_parts_equal_whole_files(torch_dev, oracle, tmp_pa
     inp = tmp_path / "in"
     inp.mkdir()
     short = lambda n: b"".join(b">s%d\n" % i + gen.wrap(gen.random_seq(rng, 9000), 80) for i in range(n))
-    files = {f"g{i}.fna": _chunk_genome(rng, int(rng.integers(3, 10))) for i in range(5)}
+    files = {f"g{i}.fna": gen.chunk_genome(rng, int(rng.integers(3, 10))) for i in range(5)}
     files["few.fna"] = short(4) + b">long\n" + gen.wrap(gen.random_seq(rng, 21000), 60) + short(3)
     files["none.fna"] = short(8)
-    files["dupa.fna"] = _chunk_genome(rng, 8)
+    files["dupa.fna"] = gen.chunk_genome(rng, 8)
     files["dupa.fa"] = b">d\n" + gen.wrap(gen.random_seq(rng, 70000), 70)
     files["dupb.fna"] = b">d\n" + gen.wrap(gen.random_seq(rng, 61000), 70)
-    files["dupb.fa"] = _chunk_genome(rng, 8)
+    files["dupb.fa"] = gen.chunk_genome(rng, 8)
     for name, b in files.items():
         (inp / name).write_bytes(b)
     assert sum(len(M.record_pieces(str(inp / f), 30000)) > 1 for f in files) >= 6
@@ -1024,7 +1002,7 @@ def test_cli_get_chunks_large_k_bounded_launches(torch_dev, oracle, tmp_path):
     inp, out = tmp_path / "in", tmp_path / "out"
     inp.mkdir()
     out.mkdir()
-    genomes = {f"h{i}": _chunk_genome(rng, 3) + b">tail\n" + gen.wrap(gen.random_seq(rng, 61000), 80)
+    genomes = {f"h{i}": gen.chunk_genome(rng, 3) + b">tail\n" + gen.wrap(gen.random_seq(rng, 61000), 80)
                for i in range(2)}
     for name, b in genomes.items():
         (inp / f"{name}.fna").write_bytes(b)
