@@ -774,6 +774,36 @@ int kf_sq_distances_tile(void);
 int kf_sq_distances(const float* d_x, uint64_t Q, const float* d_y, uint64_t B, uint64_t D,
                     float* d_out, void* stream);
 
+/* ---- classify's class probabilities (kf2vec/classify.py:117-122): for each row
+ * of d_logits[Q x C], float32, contiguous, with every operation rounded to
+ * float32 and none contracted into an fma,
+ *   m = max_j x_j; t_j = x_j - m; e_j = expf(t_j); s = sum_j e_j; p_j = e_j / s
+ * (a correctly rounded division): torch.exp(F.log_softmax(x, dim=1)) in the
+ * direct form, which keeps the digits of small probabilities that
+ * exp(x - m - log s) loses.  d_out[r, 1 + j] = p_j; d_top[r] = the lowest j
+ * whose rounded p_j is the row's largest (topk(1)'s choice among ties on the
+ * CPU); d_out[r, 0] = p[d_top[r]], the same bits: the C + 1 floats that a row
+ * of classes.out holds behind its label and class, ready for
+ * kf_format_float_rows.
+ * A row that holds a NaN or +inf, or is all -inf, is NaN in all C + 1 outputs
+ * with d_top = 0 (IEEE evaluation of the lines above; an empty genome's NaN
+ * features end here); a -inf among finite logits has p = 0.
+ * A wave owns a row, kf_class_probs_rows() = 4 rows per workgroup.  A lane adds
+ * its columns (l, l + 64, ...) in ascending order and the 64 partial sums meet
+ * in an xor butterfly, so the sum is a fixed function of C alone: a row's bits
+ * depend neither on Q, nor on its place, nor on how Q is cut into calls.  Up to
+ * kf_class_probs_reg_cols() = 1024 columns the row stays in registers, above
+ * that it is read three times.  No scratch, no memset, no allocation, no host
+ * synchronisation; asynchronous on `stream`.
+ * KF_EINVAL, before any HIP call, for C == 0, C >= 2^31, Q above 4 * (2^24 - 1)
+ * (a launch has fewer than 2^32 threads: the caller cuts Q), a null pointer
+ * with Q > 0, or a pointer not aligned to 4 bytes.  Q == 0 is valid and writes
+ * nothing. */
+int kf_class_probs_reg_cols(void);
+int kf_class_probs_rows(void);
+int kf_class_probs(const float* d_logits, uint64_t Q, uint64_t C, float* d_out /* [Q x (C+1)] */,
+                   int32_t* d_top /* [Q] */, void* stream);
+
 /* Hash of the sources this library was built from (csrc/ + this header, as
  * kf2vecfsw_amd/build.py computes it): 16 hex digits, with a "+<tag>" suffix for
  * profiling builds.  The Python binding refuses a library whose id differs from

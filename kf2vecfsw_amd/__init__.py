@@ -12,6 +12,9 @@ Layout:
                       (kf_parse_tsv_floats) and written (kf_format_float_rows, write_float_table)
   query.py            `query`: distances to a clade's backbone (kf_sq_distances) and embeddings, written
                       as text formatted on the device
+  classify.py         `classify`: the classifier's forward pass, kf_class_probs (softmax in the direct form,
+                      first-index argmax, the classes.out row) and classes.out written from the device;
+                      main.py's `process_query_data` runs get_frequencies, classify and query in turn
 """
 __all__ = ["__version__"]
 __version__ = "0.1.0"

@@ -90,6 +90,9 @@ SIGNATURES = {
     "kf_shortest_decimal_host": (_int, [_vp, _int, _int, _u64, _vp, _vp, _vp]),
     "kf_sq_distances_tile": (_int, []),
     "kf_sq_distances": (_int, [_vp, _u64, _vp, _u64, _u64, _vp, _vp]),
+    "kf_class_probs_reg_cols": (_int, []),
+    "kf_class_probs_rows": (_int, []),
+    "kf_class_probs": (_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
     "kf_write_text_segments": (_int, [_i32, ctypes.POINTER(_cp), _vp, _vp, _vp, _int]),
 }
 

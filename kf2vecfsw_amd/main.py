@@ -1370,6 +1370,37 @@ def query(args) -> None:
     Q.query(args)
 
 
+def classify(args) -> None:
+    """`classify`: the clade of every query, its probabilities computed and
+    written as text on the device (classify.classify_func; kf2vec/main.py:400-411)."""
+    from . import classify as CL
+    CL.classify(args)
+
+
+def process_query_data(args) -> None:
+    """`process_query_data`: get_frequencies, classify and query one after
+    another in this process, with the reference's banner lines and its rewiring
+    of the arguments (kf2vec/main.py:626-651).  The stages hand over through the
+    `.kf` files and classes.out in -output_dir."""
+    print("\n==> Computing k-mer frequences\n")
+    get_frequencies(args)
+
+    print("\n==> Classifying query samples\n")
+    args.input_dir = args.output_dir
+    args.model = args.classifier_model
+    args.seed = args.cl_seed
+    args.o = args.output_dir
+    classify(args)
+
+    print("\n==> Computing model distances\n")
+    args.model = args.distance_model
+    args.classes = args.output_dir
+    args.seed = args.di_seed
+    query(args)
+
+    print("\n==> Query processing step is completed!\n")
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="K-mer frequency to distance\n{}".format(__version__),
                                      formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -1380,7 +1411,11 @@ def build_parser() -> argparse.ArgumentParser:
                                             "get_frequencies          Extract k-mer frequency from a reference "
                                             "genome-skims or assemblies\n"
                                             "get_chunks               Extract chunks from reference assemblies\n"
-                                            "query                    Query models\n")
+                                            "classify                 Classifies query samples using previously "
+                                            "trained classifier model\n"
+                                            "query                    Query models\n"
+                                            "process_query_data       Wrapper command to preprocess query sequences, "
+                                            "classify and compute distances to backbone species\n")
     pf = sub.add_parser("get_frequencies", description="Process a library of reference genome-skims or assemblies")
     pf.add_argument("-input_dir", help="Directory of input genomes or assemblies "
                                        "(dir of .fastq/.fq/.fa/.fna/.fasta files)")
@@ -1444,6 +1479,51 @@ def build_parser() -> argparse.ArgumentParser:
     pq.add_argument("-o", help="Output path")
     pq.add_argument("-device", default=None, help="torch device (default: cuda)")
     pq.set_defaults(func=query)
+
+    pl = sub.add_parser("classify", description="Classifies query inputs using previously trained classifier model")
+    pl.add_argument("-input_dir", help="Directory of input k-mer frequencies for queries samples: assemblies or reads "
+                                       "(dir of .kf files for queries)")
+    pl.add_argument("-model", help="Classification model")
+    pl.add_argument("-block", type=int, default=default_block_sz,
+                    help="Block size for file processing. Default: {}".format(default_block_sz))
+    pl.add_argument("-seed", type=int, default=default_seed, help="Random seed. Default: {}".format(default_seed))
+    pl.add_argument("-o", help="Output path")
+    pl.add_argument("-device", default=None, help="torch device (default: cuda)")
+    pl.set_defaults(func=classify)
+
+    pp = sub.add_parser("process_query_data",
+                        description="Wrapper command that combines subcommands: get_frequencies (from query samples), "
+                                    "classify and query. The reference's parser defines neither -raw_cnt, -block nor "
+                                    "-remap, which its get_frequencies, classify and query read, so the command "
+                                    "cannot run there; here the three options exist, with the values the "
+                                    "subcommands default to.")
+    pp.add_argument("-input_dir", help="Directory of input genomes or assemblies "
+                                       "(dir of .fastq/.fq/.fa/.fna/.fasta files)")
+    pp.add_argument("-output_dir", help="Directory for outputs (dir for .kf files)")
+    pp.add_argument("-k", type=int, choices=list(range(3, 11)), default=default_k_len,
+                    help="K-mer length [3-10]. Default: {}".format(default_k_len), metavar="K")
+    pp.add_argument("-p", type=int, choices=list(range(1, mp.cpu_count() + 1)), default=mp.cpu_count(),
+                    help="Max number of processors to use [1-{0}]. Default for this machine: {0}".format(
+                        mp.cpu_count()), metavar="P")
+    pp.add_argument("-pseudocount", action="store_true",
+                    help="Computes k-mer counts with 0.5 pseudocount added to each frequency value")
+    pp.add_argument("-classifier_model", help="Classification model path")
+    pp.add_argument("-cl_seed", type=int, default=default_seed,
+                    help="Clssification random seed. Default: {}".format(default_seed))
+    pp.add_argument("-distance_model", help="Directory of models and embeddings (dir of model_subtree_INDEX.ckpt and "
+                                            "embeddings_subtree_INDEX.csv files for backbone)")
+    pp.add_argument("-di_seed", type=int, default=default_seed,
+                    help="Query random seed. Default: {}".format(default_seed))
+    pp.add_argument("-raw_cnt", action="store_true",
+                    help="Computes raw k-mer counts without normalization (not in the reference's parser, which "
+                         "get_frequencies needs)")
+    pp.add_argument("-block", type=int, default=default_block_sz,
+                    help="Block size for file processing in classify and query (not in the reference's parser). "
+                         "Default: {}".format(default_block_sz))
+    pp.add_argument("-remap", help='Remap file with alternative output names for query ("label" and "new_label" '
+                                   "columns in .tsv format; not in the reference's parser)")
+    pp.add_argument("-device", default=None, help="torch device (default: cuda)")
+    pp.set_defaults(func=process_query_data)
     return parser
 
 

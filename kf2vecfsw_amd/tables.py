@@ -626,12 +626,16 @@ class FloatTableWriter:
         self.times = {"copy_back": 0.0, "file_write": 0.0}
 
     def write(self, path: str, labels, values: torch.Tensor, header=None, mode: int = KF_FLOAT_SHORTEST,
-              sep: str = "\t", eol: str = "\r\n", nan_empty: bool = False, append: bool = False) -> None:
+              sep: str = "\t", eol: str = "\r\n", nan_empty: bool = False, append: bool = False,
+              quoted: bool = False) -> None:
+        """quoted: the labels are row prefixes written as given (bytes that
+        quote_label has seen already, and may hold further fields: classify's
+        label and class), not labels to quote."""
         while len(self.pending) >= self.max_pending:   # a slow disk holds the caller back, not memory
             self.pending.pop(0).result()
         values = values.contiguous()
         n, ncols = int(values.shape[0]), int(values.shape[1])
-        enc = None if labels is None else [quote_label(x, sep, eol) for x in labels]
+        enc = None if labels is None else list(labels) if quoted else [quote_label(x, sep, eol) for x in labels]
         enc, longest = _encode_labels(enc, n)
         head = header_line(header, sep, eol) if header is not None else b""
         bound = float_row_bound(ncols, longest, len(eol.encode()))
