@@ -804,6 +804,59 @@ int kf_class_probs_rows(void);
 int kf_class_probs(const float* d_logits, uint64_t Q, uint64_t C, float* d_out /* [Q x (C+1)] */,
                    int32_t* d_top /* [Q] */, void* stream);
 
+/* ---- the distance trainer's loss and its gradient (kf2vec/train_model_set.py:448-467,
+ * losses.py:13-49, utils.py:240-256): for the batch's embeddings d_y[B x E] (float32,
+ * contiguous), the clade's true distances d_true[N x N] (float64, contiguous) and the
+ * batch's labels d_labels[B] (rows and columns of d_true), over i, j in [0, B), with
+ * every operation rounded on its own and none contracted into an fma,
+ *   s_ij = 0; for e ascending: t = y_i[e] - y_j[e], s = s + t * t          (float32)
+ *   d_ij = sqrtf(s_ij)                                                     (correctly rounded)
+ *   T = d_true[l_i * N + l_j]; w = 1.0 / (T + 1e-6); r = sqrt(T); u = (double)d_ij - r
+ *   v_ij = (u * u) * w; inv = 1.0 / (double)(B * B)                        (float64)
+ *   *d_loss = (sum_i (sum_j v_ij)) * inv
+ *       (float64; both sums start at 0.0, the inner over j ascending, the outer over i
+ *       ascending; the diagonal is included, as .mean() includes it)
+ *   g_ij = (float)(((2.0 * u) * w) * inv)
+ *   c_ij = d_ij == 0 ? 0 : (g_ij + g_ji) / d_ij
+ *       (float32, a correctly rounded division; g_ji is taken at d_true[l_j * N + l_i]:
+ *       the matrix need not be symmetric; a zero distance gives a zero gradient, as
+ *       cdist's backward does)
+ *   d_grad[i, e] = 0; for j ascending: grad = grad + c_ij * (y_i[e] - y_j[e])   (float32)
+ * This is torch.cdist(y, y, compute_mode='donot_use_mm_for_euclid_dist'), the
+ * reference's Loss.my_mse_loss and autograd's backward of both down to y, in the direct
+ * form.  Every output's chain of additions is walked by one thread in the stated order,
+ * so the bits depend neither on tiles nor on the path taken, and two calls agree bit for
+ * bit; train.dist_loss_host states the same operations in numpy.
+ * NaN, negative or infinite entries of d_true and NaN embeddings follow IEEE
+ * evaluation of the lines above; nothing is special-cased.  Repeated labels are valid.
+ * A label outside [0, N) sets *d_status = 1 and makes *d_loss NaN (the gradient is then
+ * NaN wherever a non-zero distance enters it, and not to be used: the caller goes by
+ * the status), and nothing is read out of bounds; otherwise *d_status = 0.  d_grad == NULL
+ * gives the loss alone, with the same bits (the test-set pass).
+ * Up to kf_dist_loss_small_b() = 32 rows one workgroup does everything in one launch
+ * and no scratch is needed (d_scratch may be NULL).  Above, five launches: d by tiles of
+ * kf_dist_loss_tile() = 32 rows, E walked in slices of kf_dist_loss_depth() = 32
+ * columns through LDS; one thread per pair; the row sums; the total with the labels'
+ * check; and d_grad by tiles of 32 rows x 32 columns, j walked in slices of 32.
+ * kf_dist_loss_scratch_bytes gives the scratch for B rows (12 * B * B + 8 * B bytes
+ * above 32 rows).  The call allocates nothing, sets no memory and never waits for the
+ * device: it is asynchronous on `stream`, and all scratch is the caller's.
+ * KF_EINVAL, before any HIP call, for B == 0, E == 0, B above kf_dist_loss_max_b() =
+ * 8192, E above 2^24, N == 0 or N >= 2^30, a null d_y, d_true, d_labels, d_loss or
+ * d_status, a null d_scratch where scratch is needed, a scratch that is too small, or a
+ * pointer not aligned to its element (8 bytes for d_true, d_labels, d_loss and
+ * d_scratch, 4 for d_y, d_grad and d_status). */
+int kf_dist_loss_small_b(void);
+int kf_dist_loss_tile(void);
+int kf_dist_loss_depth(void);
+uint64_t kf_dist_loss_max_b(void);
+int kf_dist_loss_scratch_bytes(uint64_t B, uint64_t* bytes);
+int kf_dist_loss(const float* d_y, uint64_t B, uint64_t E,            /* embeddings [B x E] */
+                 const double* d_true, uint64_t N,                    /* true distances [N x N] */
+                 const int64_t* d_labels,                             /* [B], rows/cols of d_true */
+                 double* d_loss, float* d_grad /* [B x E] or NULL */,
+                 int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* Hash of the sources this library was built from (csrc/ + this header, as
  * kf2vecfsw_amd/build.py computes it): 16 hex digits, with a "+<tag>" suffix for
  * profiling builds.  The Python binding refuses a library whose id differs from

@@ -93,6 +93,12 @@ SIGNATURES = {
     "kf_class_probs_reg_cols": (_int, []),
     "kf_class_probs_rows": (_int, []),
     "kf_class_probs": (_int, [_vp, _u64, _u64, _vp, _vp, _vp]),
+    "kf_dist_loss_small_b": (_int, []),
+    "kf_dist_loss_tile": (_int, []),
+    "kf_dist_loss_depth": (_int, []),
+    "kf_dist_loss_max_b": (_u64, []),
+    "kf_dist_loss_scratch_bytes": (_int, [_u64, _P64]),
+    "kf_dist_loss": (_int, [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "kf_write_text_segments": (_int, [_i32, ctypes.POINTER(_cp), _vp, _vp, _vp, _int]),
 }
 

@@ -26,6 +26,13 @@ __version__ = "kf2vec 0.1.3 (kf2vecfsw_amd MI355X)"
 default_k_len = 7          # main.py:80
 default_seed = 28          # main.py:97
 default_block_sz = 4000    # main.py:98
+default_hidden_sz = 2048   # main.py:86
+default_embed_sz = 1024    # main.py:87
+default_batch_sz = 16      # main.py:88
+default_di_epochs = 8000   # main.py:91
+default_lr = 0.00001       # main.py:93
+default_lr_min = 3e-6      # main.py:94
+default_lr_decay = 2000    # main.py:95
 min_k_len = 2              # main.py:81
 max_k_len = 31             # main.py:82
 supported_k = range(3, 12)  # rule-generated vocab (reference ships 3..9; 10 is a missing blob)
@@ -1377,6 +1384,14 @@ def classify(args) -> None:
     CL.classify(args)
 
 
+def train_model_set(args) -> None:
+    """`train_model_set`: the distance model of every clade, trained on the
+    device with kf_dist_loss (train.train_model_set_func; kf2vec/main.py:506-531).
+    Only the NeuralNet model (-no_fsw) is trained."""
+    from . import train as TR
+    TR.train_model_set(args)
+
+
 def process_query_data(args) -> None:
     """`process_query_data`: get_frequencies, classify and query one after
     another in this process, with the reference's banner lines and its rewiring
@@ -1411,6 +1426,7 @@ def build_parser() -> argparse.ArgumentParser:
                                             "get_frequencies          Extract k-mer frequency from a reference "
                                             "genome-skims or assemblies\n"
                                             "get_chunks               Extract chunks from reference assemblies\n"
+                                            "train_model_set          Trains individual models for each subtree\n"
                                             "classify                 Classifies query samples using previously "
                                             "trained classifier model\n"
                                             "query                    Query models\n"
@@ -1463,6 +1479,39 @@ def build_parser() -> argparse.ArgumentParser:
     pc.add_argument("-batch_gb", type=float, default=1.0, help="Window bytes per device batch (GiB)")
     pc.add_argument("-device", default=None, help="torch device (default: cuda)")
     pc.set_defaults(func=get_chunks)
+
+    pt = sub.add_parser("train_model_set", description="Trains individual models for each subtree")
+    pt.add_argument("-input_dir", help="Directory of input k-mer frequencies for assemblies or reads "
+                                       "(dir of .kf files for backbone)")
+    pt.add_argument("-test_set", help="File that contains list of filenames (no extension) to be used as a test set "
+                                      "(list of .kf files for test subset)")
+    pt.add_argument("-true_dist", help="Directory of distamce matrices for backbone subtrees "
+                                       "(dir of *subtree_INDEX.di_mtrx files for backbone)")
+    pt.add_argument("-subtrees", help="Classification file with subtrees information obtained from divide_tree "
+                                      "command (a .subtrees format)")
+    pt.add_argument("-e", type=int, default=default_di_epochs,
+                    help="Number of epochs. Default: {}".format(default_di_epochs))
+    pt.add_argument("-hidden_sz", type=int, default=default_hidden_sz,
+                    help="Hidden size. Default: {}".format(default_hidden_sz))
+    pt.add_argument("-embed_sz", type=int, default=default_embed_sz,
+                    help="Embedding size. Default: {}".format(default_embed_sz))
+    pt.add_argument("-batch_sz", type=int, default=default_batch_sz,
+                    help="Batch size. Default: {}".format(default_batch_sz))
+    pt.add_argument("-lr", type=float, default=default_lr, help="Start learning rate. Default: {}".format(default_lr))
+    pt.add_argument("-lr_min", type=float, default=default_lr_min,
+                    help="Minimum learning rate. Default: {}".format(default_lr_min))
+    pt.add_argument("-lr_decay", type=float, default=default_lr_decay,
+                    help="Learning rate decay. Default: {}".format(default_lr_decay))
+    pt.add_argument("-clade", type=int, nargs="*", help="Clade number to train. Default: all")
+    pt.add_argument("-save_interval", type=int, help="Save model after specified interval of epochs. Default: last")
+    pt.add_argument("-seed", type=int, default=default_seed, help="Random seed. Default: {}".format(default_seed))
+    pt.add_argument("-o", help="Model output path")
+    pt.add_argument("-no_fsw", action="store_true", help="Keep original model (the only one trained here: the FSW "
+                                                         "model needs fswlib)")
+    pt.add_argument("-fswout_dim", type=int, default=512)
+    pt.add_argument("-base_dim", type=int, default=4)
+    pt.add_argument("-device", default=None, help="torch device (default: cuda)")
+    pt.set_defaults(func=train_model_set)
 
     pq = sub.add_parser("query", description="Query models")
     pq.add_argument("-input_dir", help="Directory of input k-mer frequencies for assemblies or reads "
