@@ -857,6 +857,67 @@ int kf_dist_loss(const float* d_y, uint64_t B, uint64_t E,            /* embeddi
                  double* d_loss, float* d_grad /* [B x E] or NULL */,
                  int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- the classifier trainer's loss, its gradient, the batch's right classes and the
+ * epoch's totals (kf2vec/train_classifier_model.py:323-342): for the batch's logits
+ * d_logits[B x C] (float32, contiguous; the output of fc3, the softmax is the kernel's)
+ * and its classes d_true[B] (int64), per row i with c = d_true[i], every operation rounded
+ * to float32 and none contracted into an fma,
+ *   m = max_j x_j; t_j = x_j - m; e_j = expf(t_j); s = sum_j e_j; p_j = e_j / s
+ *       (kf_class_probs' own lines, in its order of the sum -- lane l adds the columns l,
+ *       l + 64, ... ascending, then the xor butterfly -- and with its correctly rounded
+ *       division: p_j has the bits kf_class_probs writes)
+ *   nll_i = logf(s) - t_c
+ *   hit_i = (the lowest j whose p_j is the row's largest) == c       (kf_class_probs' d_top)
+ *   g_ij  = (p_j - (j == c ? 1.0f : 0.0f)) * invB,  invB = 1.0f / (float)B
+ * and per call
+ *   *d_loss   = (sum_i (double)nll_i) * (1.0 / (double)B)
+ *       (float64; the sum starts at 0.0 and one thread adds the rows with i ascending, on
+ *       either path: the order is a fixed function of B alone)
+ *   *d_hits   = sum_i hit_i
+ *   *d_status = 1 if any d_true[i] is outside [0, C), else 0.
+ * This is F.log_softmax, nn.NLLLoss() (mean), autograd's backward of both down to the
+ * logits, and exp / topk(1) / accuracy_score, in the direct form;
+ * train_classifier.class_loss_host states it in numpy.  d_grad[B x C] may be NULL: the loss
+ * alone, the same bits.  d_row_loss[B] may be NULL; else it receives the nll_i.
+ * d_totals[3] (float64) may be NULL; else the finishing thread does
+ *   totals[0] += *d_loss * (double)B; totals[1] += *d_hits; totals[2] += *d_status
+ * with plain loads and stores in stream order: calls that share a totals buffer must go on
+ * one stream (no atomic is used, one thread does it), and the caller zeroes the buffer.
+ * Against the float64 value of log(sum_j exp(t_j)) - t_c from the same float32 logits, with
+ * T = sum_j p_j |t_j| (at most the largest finite |t_j|) and beside kf_class_probs'
+ * (|t_j| + C + 8) * 2^-24:
+ *   |nll_i - nll| <= (T + C + 8 + 4 |log s| + |t_c| + |nll|) * 2^-24 + C * 2^-126
+ * -- s carries the subtractions' |t_j| * 2^-24 through exp, expf's 2 units and C - 1
+ * additions of positives, relative, which log turns into an absolute error; logf is held to
+ * 2 units of log s; t_c and the last subtraction are rounded once each; an e_j below
+ * 2^-126 may be flushed to 0 while s >= 1.
+ * A row that holds a NaN or +inf, or is all -inf (kf_class_probs' NaN rows), has nll_i NaN,
+ * its gradient row NaN and hit_i 0; the loss is then NaN and the status 0.  A -inf logit
+ * among finite ones has p = 0; if it is the true class, nll_i = +inf.  A class outside
+ * [0, C) gives status 1, that row's nll_i and gradient row NaN and hit_i 0, and nothing is
+ * read out of bounds.  C == 1 is valid (p = 1, nll = 0, g = 0).  Repeated classes are the
+ * normal case.  A row's nll_i and p_j depend neither on B, nor on its place, nor on the path.
+ * A wave owns a row, in kf_class_probs' register tiers (1, 4 or 16 values per lane, three
+ * reads above kf_class_probs_reg_cols() columns).  Up to kf_class_loss_small_b() = 64 rows
+ * one workgroup does everything in one launch and no scratch is needed (d_scratch may be
+ * NULL).  Above, two launches: the rows (4 per workgroup) leave nll_i and hit_i in the
+ * caller's scratch, and one workgroup finishes.  kf_class_loss_scratch_bytes gives the
+ * scratch for B rows (8 * B bytes above 64 rows).  The call allocates nothing, sets no
+ * memory and never waits for the device: it is asynchronous on `stream`.
+ * KF_EINVAL, before any HIP call, for B == 0, C == 0, C >= 2^31, B above
+ * kf_class_loss_max_b() = 65536, a null d_logits, d_true, d_loss, d_hits or d_status, a
+ * null d_scratch where scratch is needed, a scratch that is too small, or a pointer not
+ * aligned to its element (8 bytes for d_true, d_loss, d_totals and d_scratch, 4 for
+ * d_logits, d_grad, d_row_loss, d_hits and d_status). */
+int kf_class_loss_small_b(void);
+uint64_t kf_class_loss_max_b(void);
+int kf_class_loss_scratch_bytes(uint64_t B, uint64_t* bytes);
+int kf_class_loss(const float* d_logits, uint64_t B, uint64_t C,      /* logits [B x C] */
+                  const int64_t* d_true,                              /* [B], classes */
+                  double* d_loss, float* d_grad /* [B x C] or NULL */, float* d_row_loss /* [B] or NULL */,
+                  int32_t* d_hits, int32_t* d_status, double* d_totals /* [3] or NULL */,
+                  void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* Hash of the sources this library was built from (csrc/ + this header, as
  * kf2vecfsw_amd/build.py computes it): 16 hex digits, with a "+<tag>" suffix for
  * profiling builds.  The Python binding refuses a library whose id differs from

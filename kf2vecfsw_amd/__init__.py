@@ -15,6 +15,11 @@ Layout:
   classify.py         `classify`: the classifier's forward pass, kf_class_probs (softmax in the direct form,
                       first-index argmax, the classes.out row) and classes.out written from the device;
                       main.py's `process_query_data` runs get_frequencies, classify and query in turn
+  train.py            `train_model_set`: the distance model of every clade, a step's loss and gradient in
+                      one call (kf_dist_loss)
+  train_classifier.py `train_classifier`: the clade classifier, a step's loss, gradient, right classes and
+                      the epoch's totals in one call (kf_class_loss); writes classifier_model.ckpt and
+                      backbone_classes.out
 """
 __all__ = ["__version__"]
 __version__ = "0.1.0"

@@ -99,6 +99,10 @@ SIGNATURES = {
     "kf_dist_loss_max_b": (_u64, []),
     "kf_dist_loss_scratch_bytes": (_int, [_u64, _P64]),
     "kf_dist_loss": (_int, [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "kf_class_loss_small_b": (_int, []),
+    "kf_class_loss_max_b": (_u64, []),
+    "kf_class_loss_scratch_bytes": (_int, [_u64, _P64]),
+    "kf_class_loss": (_int, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "kf_write_text_segments": (_int, [_i32, ctypes.POINTER(_cp), _vp, _vp, _vp, _int]),
 }
 

@@ -20,10 +20,11 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES_HIP = ["kf_count.hip", "kf_bucket.hip", "kf_chunks.hip", "kf_sparse.hip", "kf_index.hip", "kf_rows.hip",
                "kf_kmers.hip", "kf_merge.hip", "kf_chunkfeat.hip", "kf_kfparse.hip", "kf_kfformat.hip", "kf_kffloat.hip",
-               "kf_tsvfloat.hip", "kf_floatformat.hip", "kf_sqdist.hip", "kf_classprobs.hip", "kf_distloss.hip"]
+               "kf_tsvfloat.hip", "kf_floatformat.hip", "kf_sqdist.hip", "kf_classprobs.hip", "kf_distloss.hip",
+               "kf_classloss.hip"]
 SOURCES_CPP = ["kf_host.cpp"]
 DEPS = SOURCES_HIP + SOURCES_CPP + ["kf_internal.h", "kf_front.h", "kf_scan.h", "kf_compact.h", "kf_kfrows.h", "kf_decimal.h",
-                                     "kf_floatfield.h", "kf_shortest.h", "../../include/kf2vec_gpu.h"]
+                                     "kf_floatfield.h", "kf_shortest.h", "kf_softmax.h", "../../include/kf2vec_gpu.h"]
 
 
 def source_id() -> str:
@@ -76,7 +77,7 @@ def build(force: bool = False, verbose: bool = False, ablation: bool = False, ou
 
 
 HEADERS = ["kf_internal.h", "kf_front.h", "kf_scan.h", "kf_compact.h", "kf_kfrows.h", "kf_decimal.h", "kf_floatfield.h",
-           "kf_shortest.h", "../../include/kf2vec_gpu.h"]
+           "kf_shortest.h", "kf_softmax.h", "../../include/kf2vec_gpu.h"]
 
 _TOOLCHAIN: list[bytes] = []
 

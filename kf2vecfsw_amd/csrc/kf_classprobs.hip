@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "kf_internal.h"
+#include "kf_softmax.h"                          // the row softmax, shared with kf_classloss.hip
 
 // as in kf_sqdist.hip: no product and sum of this file may become an fma
 #pragma clang fp contract(off)
@@ -35,40 +36,13 @@
 namespace kf {
 namespace {
 
-constexpr int kPWave = 64;
+using softmax::wave_best;
+
+constexpr int kPWave = softmax::kWave;
 constexpr int kPRows = 4;                       // rows (waves) per workgroup
 constexpr int kPBlock = kPWave * kPRows;
-constexpr int kPRegTiles = 16;                  // values per lane at most while the row stays in registers
-constexpr int kRegCols = kPWave * kPRegTiles;   // 1024
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kPWave));
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, kPWave);
-    return v;
-}
-
-__device__ __forceinline__ int wave_any(int v) { return __any(v); }
-
-// the largest value and, among equals, the lowest index
-__device__ __forceinline__ void wave_best(float& v, uint32_t& i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, kPWave);
-        const uint32_t oi = (uint32_t)__shfl_xor((int)i, o, kPWave);
-        if (ov > v || (ov == v && oi < i)) {
-            v = ov;
-            i = oi;
-        }
-    }
-}
-
-__device__ __forceinline__ bool refused(float x) { return x != x || x == INFINITY; }
+constexpr int kPRegTiles = softmax::kRegTiles;  // values per lane at most while the row stays in registers
+constexpr int kRegCols = softmax::kRegCols;     // 1024
 
 __device__ __forceinline__ void nan_row(float* __restrict__ o, int32_t* __restrict__ top, uint64_t r, uint32_t C,
                                         uint32_t lane) {
@@ -86,73 +60,19 @@ __global__ void __launch_bounds__(kPBlock) class_probs_kernel(const float* __res
     if (r >= Q) return;                          // a whole wave leaves: nothing below waits for another wave
     const float* __restrict__ x = logits + r * C;
     float* __restrict__ o = out + r * ((uint64_t)C + 1);
-    float m = -INFINITY;
-    int bad = 0;
+    float m, s;
     float best = -1.0f;                          // below every probability
     uint32_t besti = 0xffffffffu;
-    if constexpr (NT > 0) {
-        float v[NT];
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const uint32_t j = lane + (uint32_t)i * kPWave;
-            v[i] = j < C ? x[j] : -INFINITY;
-            bad |= refused(v[i]);
-            m = fmaxf(m, v[i]);
+    const bool ok = softmax::row<NT>(x, C, lane, m, s, [&](uint32_t j, float p) {
+        o[1 + (uint64_t)j] = p;
+        if (p > best) {                          // ascending j: the first of equals stays
+            best = p;
+            besti = j;
         }
-        m = wave_max(m);
-        if (wave_any(bad) || m == -INFINITY) {
-            nan_row(o, top, r, C, lane);
-            return;
-        }
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const uint32_t j = lane + (uint32_t)i * kPWave;
-            if (j < C) {
-                const float t = v[i] - m;
-                v[i] = expf(t);
-                s = s + v[i];
-            }
-        }
-        s = wave_sum(s);
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            const uint32_t j = lane + (uint32_t)i * kPWave;
-            if (j < C) {
-                const float p = __fdiv_rn(v[i], s);
-                o[1 + (uint64_t)j] = p;
-                if (p > best) {                  // ascending j: the first of equals stays
-                    best = p;
-                    besti = j;
-                }
-            }
-        }
-    } else {
-        for (uint32_t j = lane; j < C; j += kPWave) {
-            const float xv = x[j];
-            bad |= refused(xv);
-            m = fmaxf(m, xv);
-        }
-        m = wave_max(m);
-        if (wave_any(bad) || m == -INFINITY) {
-            nan_row(o, top, r, C, lane);
-            return;
-        }
-        float s = 0.0f;
-        for (uint32_t j = lane; j < C; j += kPWave) {
-            const float t = x[j] - m;
-            s = s + expf(t);
-        }
-        s = wave_sum(s);
-        for (uint32_t j = lane; j < C; j += kPWave) {
-            const float t = x[j] - m;
-            const float p = __fdiv_rn(expf(t), s);
-            o[1 + (uint64_t)j] = p;
-            if (p > best) {
-                best = p;
-                besti = j;
-            }
-        }
+    });
+    if (!ok) {
+        nan_row(o, top, r, C, lane);
+        return;
     }
     wave_best(best, besti);
     if (lane == 0) {

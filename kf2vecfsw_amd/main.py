@@ -29,6 +29,7 @@ default_block_sz = 4000    # main.py:98
 default_hidden_sz = 2048   # main.py:86
 default_embed_sz = 1024    # main.py:87
 default_batch_sz = 16      # main.py:88
+default_cl_epochs = 2000   # main.py:90
 default_di_epochs = 8000   # main.py:91
 default_lr = 0.00001       # main.py:93
 default_lr_min = 3e-6      # main.py:94
@@ -1392,6 +1393,14 @@ def train_model_set(args) -> None:
     TR.train_model_set(args)
 
 
+def train_classifier(args) -> None:
+    """`train_classifier`: the clade classifier of a library, trained on the
+    device with kf_class_loss (train_classifier.train_classifier_model_func;
+    kf2vec/main.py:376-397)."""
+    from . import train_classifier as TC
+    TC.train_classifier(args)
+
+
 def process_query_data(args) -> None:
     """`process_query_data`: get_frequencies, classify and query one after
     another in this process, with the reference's banner lines and its rewiring
@@ -1426,6 +1435,8 @@ def build_parser() -> argparse.ArgumentParser:
                                             "get_frequencies          Extract k-mer frequency from a reference "
                                             "genome-skims or assemblies\n"
                                             "get_chunks               Extract chunks from reference assemblies\n"
+                                            "train_classifier         Train classifier model based on backbone "
+                                            "subtrees\n"
                                             "train_model_set          Trains individual models for each subtree\n"
                                             "classify                 Classifies query samples using previously "
                                             "trained classifier model\n"
@@ -1479,6 +1490,28 @@ def build_parser() -> argparse.ArgumentParser:
     pc.add_argument("-batch_gb", type=float, default=1.0, help="Window bytes per device batch (GiB)")
     pc.add_argument("-device", default=None, help="torch device (default: cuda)")
     pc.set_defaults(func=get_chunks)
+
+    pa = sub.add_parser("train_classifier", description="Train classifier model based on backbone subtrees")
+    pa.add_argument("-input_dir", help="Directory of input k-mer frequencies for assemblies or reads "
+                                       "(dir of .kf files for backbone)")
+    pa.add_argument("-subtrees", help="Classification file with subtrees information obtained from divide_tree "
+                                      "command (a .subtrees format)")
+    pa.add_argument("-e", type=int, default=default_cl_epochs,
+                    help="Number of epochs. Default: {}".format(default_cl_epochs))
+    pa.add_argument("-hidden_sz", type=int, default=default_hidden_sz,
+                    help="Hidden size. Default: {}".format(default_hidden_sz))
+    pa.add_argument("-batch_sz", type=int, default=default_batch_sz,
+                    help="Batch size. Default: {}".format(default_batch_sz))
+    pa.add_argument("-lr", type=float, default=default_lr, help="Start learning rate. Default: {}".format(default_lr))
+    pa.add_argument("-lr_min", type=float, default=default_lr_min,
+                    help="Minimum learning rate. Default: {}".format(default_lr_min))
+    pa.add_argument("-lr_decay", type=float, default=default_lr_decay,
+                    help="Learning rate decay. Default: {}".format(default_lr_decay))
+    pa.add_argument("-seed", type=int, default=default_seed, help="Random seed. Default: {}".format(default_seed))
+    pa.add_argument("-mask", action="store_true", help=argparse.SUPPRESS)
+    pa.add_argument("-o", help="Model output path")
+    pa.add_argument("-device", default=None, help="torch device (default: cuda)")
+    pa.set_defaults(func=train_classifier)
 
     pt = sub.add_parser("train_model_set", description="Trains individual models for each subtree")
     pt.add_argument("-input_dir", help="Directory of input k-mer frequencies for assemblies or reads "
