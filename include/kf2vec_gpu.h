@@ -857,6 +857,29 @@ int kf_dist_loss(const float* d_y, uint64_t B, uint64_t E,            /* embeddi
                  double* d_loss, float* d_grad /* [B x E] or NULL */,
                  int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* ---- the chunk trainer's loss and its gradient (kf2vec/train_model_set_chunks.py:392-418,
+ * losses.py:58-117): kf_dist_loss' contract, line for line, with two changes.  `views`
+ * rows that follow each other are views of one genome and share its label: row i's label
+ * is d_labels[i / views] (torch.repeat_interleave(labels, views)), so d_labels holds
+ * B / views entries.  And the weight is w = 1.0 / (T + eps), on the side of
+ * T = d_true[l_i * N + l_j] and on that of d_true[l_j * N + l_i] (Loss_chunks has
+ * eps = 1000).  The rest is kf_dist_loss': the float32 direct-form distances, the float64
+ * pair terms, both sums in ascending order from 0.0, inv = 1.0 / (double)(B * B) over all
+ * B rows with the diagonal and the pairs of one genome's views included, c_ij = 0 where
+ * d_ij == 0 (two equal views), no fma, status 1 and a NaN loss for a label outside [0, N)
+ * with nothing read out of bounds, d_grad == NULL for the loss alone, one workgroup up to
+ * kf_dist_loss_small_b() rows (rows, not labels) and five launches above, the scratch of
+ * kf_dist_loss_scratch_bytes(B), no allocation, memset or wait.  kf_dist_loss is this call
+ * with views = 1 and eps = 1e-6, the same code and the same bits;
+ * train.dist_loss_host(..., views, eps) states both in numpy.
+ * KF_EINVAL, before any HIP call, for kf_dist_loss' cases and for views == 0, B no
+ * multiple of views, and an eps that is NaN, infinite or negative. */
+int kf_dist_loss_views(const float* d_y, uint64_t B, uint64_t E,      /* embeddings [B x E] */
+                       const double* d_true, uint64_t N,              /* true distances [N x N] */
+                       const int64_t* d_labels /* [B / views] */, uint64_t views, double eps,
+                       double* d_loss, float* d_grad /* [B x E] or NULL */,
+                       int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* ---- the classifier trainer's loss, its gradient, the batch's right classes and the
  * epoch's totals (kf2vec/train_classifier_model.py:323-342): for the batch's logits
  * d_logits[B x C] (float32, contiguous; the output of fc3, the softmax is the kernel's)

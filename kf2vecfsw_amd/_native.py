@@ -99,6 +99,8 @@ SIGNATURES = {
     "kf_dist_loss_max_b": (_u64, []),
     "kf_dist_loss_scratch_bytes": (_int, [_u64, _P64]),
     "kf_dist_loss": (_int, [_vp, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "kf_dist_loss_views": (_int, [_vp, _u64, _u64, _vp, _u64, _vp, _u64, ctypes.c_double, _vp, _vp, _vp, _vp, _u64,
+                                  _vp]),
     "kf_class_loss_small_b": (_int, []),
     "kf_class_loss_max_b": (_u64, []),
     "kf_class_loss_scratch_bytes": (_int, [_u64, _P64]),

@@ -625,7 +625,7 @@ def features(counts: torch.Tensor, pseudocount: bool = False, raw_cnt: bool = Fa
 
 def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | None = None,
                    dtype: torch.dtype = torch.float32, out: torch.Tensor | None = None,
-                   stream: int | None = None) -> torch.Tensor:
+                   stream: int | None = None, check: bool = True):
     """In-memory hand-off of get_chunks to the chunk trainer (kf_chunk_features):
     [S, nbins] of `dtype` (float32 or float64), row s the column-wise sum of the
     window rows counts[lo[s]: lo[s] + n[s]] (each count as min(count, cap) if
@@ -639,7 +639,10 @@ def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | 
     lo, n: host arrays (one staged pinned copy), or int64 tensors on the device.
     The device checks the table; its status word is read back here (the call's
     one synchronisation) and a sample outside [0, n_rows] raises N.NativeError
-    with `out` untouched."""
+    with `out` untouched.  check=False (lo and n on the device): nothing waits,
+    and (out, status) come back, status the int32 [1] word on the device, not
+    zero where a sample lay outside -- the caller reads it with its own next
+    read (the chunk trainer: once per epoch)."""
     assert counts.dtype in (torch.int16, torch.int32) and counts.dim() == 2 and counts.is_contiguous()
     assert dtype in (torch.float32, torch.float64)
     dev = counts.device
@@ -658,7 +661,7 @@ def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | 
         out = torch.empty((ns, nbins), dtype=dtype, device=dev)
     assert out.dtype == dtype and out.shape == (ns, nbins) and out.is_contiguous() and out.device == dev
     if ns == 0:
-        return out
+        return out if check else (out, torch.zeros(1, dtype=torch.int32, device=dev))
     status = torch.empty(1, dtype=torch.int32, device=dev)
     need = int(N.lib().kf_chunk_features_scratch_bytes(ns))
     work = torch.empty(need // 8, dtype=torch.int64, device=dev)
@@ -668,6 +671,10 @@ def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | 
             counts.data_ptr() if counts.shape[0] else None, counts.element_size(), counts.shape[0], nbins,
             d_lo.data_ptr(), d_n.data_ptr(), ns, 0xFFFFFFFF if cap is None else int(cap), float(scaler),
             out.data_ptr(), out.element_size(), status.data_ptr(), work.data_ptr(), need, s), "kf_chunk_features")
+    if not check:
+        if stream is not None:   # the work table is the caller's stream's until the call is done
+            work.record_stream(torch.cuda.ExternalStream(stream, device=dev))
+        return out, status
     if stream is not None:   # the read-back below is ordered on torch's current stream only
         torch.cuda.synchronize(dev)
     if int(status.item()) != 0:

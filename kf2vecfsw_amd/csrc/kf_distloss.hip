@@ -1,12 +1,12 @@
-// kf_distloss.hip -- kf_dist_loss: the distance trainer's weighted loss of a batch and its
-// gradient with respect to the embeddings, with the order of every sum fixed.
+// kf_distloss.hip -- kf_dist_loss and kf_dist_loss_views: the distance trainers' weighted loss
+// of a batch and its gradient with respect to the embeddings, with the order of every sum fixed.
 //
 // For embeddings y[B x E] (float32), the clade's true distances P[N x N] (float64) and the
 // batch's labels l[B] (rows and columns of P), over i, j in [0, B)
 // (kf2vec/train_model_set.py:448-467, losses.py:13-49, utils.py:240-256):
 //   s_ij = 0;  for e ascending: t = y_i[e] - y_j[e], s = s + t * t        (float32)
 //   d_ij = sqrtf(s_ij)                                                     (correctly rounded)
-//   T = P[l_i, l_j];  w = 1 / (T + 1e-6);  r = sqrt(T);  u = (double)d_ij - r
+//   T = P[l_i, l_j];  w = 1 / (T + eps);  r = sqrt(T);  u = (double)d_ij - r
 //   v_ij = (u * u) * w;  inv = 1 / (double)(B * B)                         (float64)
 //   loss = (sum_i (sum_j v_ij)) * inv       (float64, both sums from 0.0, j and i ascending)
 //   g_ij = (float)(((2 * u) * w) * inv)
@@ -17,6 +17,12 @@
 // backward of both in the direct form; train.dist_loss_host states it in numpy, and the
 // kernels equal it bit for bit whatever path they take, because every output's chain of
 // additions is walked by one thread in the stated order.
+//
+// kf_dist_loss has a label per row and eps = 1e-6.  kf_dist_loss_views is the chunk trainer's
+// (kf2vec/train_model_set_chunks.py:392-418, losses.py:58-117): `views` rows that follow each
+// other share a label, l_i = labels[i / views] (torch.repeat_interleave), and eps is the
+// caller's (Loss_chunks has 1000).  Both are one code: the labels' load, pair_terms and the
+// labels' check are the three places that know of either.
 //
 // s_ij and s_ji are the same bits (t and -t have the same square), so d is symmetric and
 // the element at [j, i] serves as d_ij: the pair kernel reads, and the gradient kernel's
@@ -65,9 +71,9 @@ constexpr int kLSumChunk = 1024;              // row sums per LDS load of the to
 typedef float vLf __attribute__((ext_vector_type(kLPer)));
 
 // v_ij, and c_ij if want_c, of one pair: d = d_ij (= d_ji), tij = P[l_i, l_j], tji = P[l_j, l_i]
-__device__ __forceinline__ void pair_terms(float d, double tij, double tji, double inv, bool want_c, double& v,
-                                           float& c) {
-    const double w = 1.0 / (tij + 1e-6);
+__device__ __forceinline__ void pair_terms(float d, double tij, double tji, double eps, double inv, bool want_c,
+                                           double& v, float& c) {
+    const double w = 1.0 / (tij + eps);
     const double r = sqrt(tij);
     const double u = (double)d - r;
     const double uu = u * u;
@@ -77,7 +83,7 @@ __device__ __forceinline__ void pair_terms(float d, double tij, double tji, doub
         const double a = 2.0 * u;
         const double aw = a * w;
         const float gij = (float)(aw * inv);
-        const double w2 = 1.0 / (tji + 1e-6);
+        const double w2 = 1.0 / (tji + eps);
         const double r2 = sqrt(tji);
         const double u2 = (double)d - r2;
         const double a2 = 2.0 * u2;
@@ -90,13 +96,16 @@ __device__ __forceinline__ void pair_terms(float d, double tij, double tji, doub
 
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
+// the place of row i's label: `views` rows that follow each other share one (i < 2^13)
+__device__ __forceinline__ uint32_t label_of(uint32_t i, uint32_t views) { return views == 1 ? i : i / views; }
+
 // ---------------------------------------------------------------------------
 // B <= kLSmallB: one workgroup
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(kLSmallBlock) dist_loss_small_kernel(
     const float* __restrict__ y, uint32_t B, uint64_t E, const double* __restrict__ P, uint64_t N,
-    const int64_t* __restrict__ labels, double* __restrict__ loss, float* __restrict__ grad,
-    int32_t* __restrict__ status) {
+    const int64_t* __restrict__ labels, uint32_t views, double eps, double* __restrict__ loss,
+    float* __restrict__ grad, int32_t* __restrict__ status) {
     __shared__ float ys[kLSmallB][kLSmallDepth + 1];
     __shared__ double vs[kLSmallB][kLSmallB + 1];
     __shared__ float cs[kLSmallB][kLSmallB + 1];
@@ -105,7 +114,7 @@ __global__ void __launch_bounds__(kLSmallBlock) dist_loss_small_kernel(
     const uint32_t tid = threadIdx.x;
     int mine_bad = 0;
     if (tid < B) {
-        const int64_t l = labels[tid];
+        const int64_t l = labels[label_of(tid, views)];
         lab[tid] = l;
         mine_bad = l < 0 || (uint64_t)l >= N;
     }
@@ -144,7 +153,7 @@ __global__ void __launch_bounds__(kLSmallBlock) dist_loss_small_kernel(
         }
         double v;
         float c;
-        pair_terms(d, tij, tji, inv, grad != nullptr, v, c);
+        pair_terms(d, tij, tji, eps, inv, grad != nullptr, v, c);
         vs[i][j] = v;
         cs[i][j] = c;
     }
@@ -248,11 +257,12 @@ __global__ void __launch_bounds__(kLBlock) dist_kernel(const float* __restrict__
 // vT[j, i] and, if want_c, c_ij over d at [j, i]
 __global__ void __launch_bounds__(kLBlock) pair_kernel(float* __restrict__ dc, double* __restrict__ vT, uint64_t B,
                                                        const double* __restrict__ P, uint64_t N,
-                                                       const int64_t* __restrict__ labels, int want_c) {
+                                                       const int64_t* __restrict__ labels, uint32_t views, double eps,
+                                                       int want_c) {
     const uint64_t x = (uint64_t)blockIdx.x * kLBlock + threadIdx.x;
     if (x >= B * B) return;
     const uint64_t j = x / B, i = x - j * B;
-    const int64_t li = labels[i], lj = labels[j];
+    const int64_t li = labels[label_of((uint32_t)i, views)], lj = labels[label_of((uint32_t)j, views)];
     double tij = quiet_nan(), tji = quiet_nan();
     if (li >= 0 && (uint64_t)li < N && lj >= 0 && (uint64_t)lj < N) {
         tij = P[(uint64_t)li * N + (uint64_t)lj];
@@ -261,7 +271,7 @@ __global__ void __launch_bounds__(kLBlock) pair_kernel(float* __restrict__ dc, d
     const double inv = 1.0 / (double)(B * B);
     double v;
     float c;
-    pair_terms(dc[x], tij, tji, inv, want_c != 0, v, c);
+    pair_terms(dc[x], tij, tji, eps, inv, want_c != 0, v, c);
     vT[x] = v;
     if (want_c) dc[x] = c;
 }
@@ -279,11 +289,12 @@ __global__ void __launch_bounds__(64) rows_kernel(const double* __restrict__ vT,
 
 // one workgroup: the labels' check, the row sums added in order, loss and status
 __global__ void __launch_bounds__(kLBlock) total_kernel(const double* __restrict__ rsum, uint64_t B,
-                                                        const int64_t* __restrict__ labels, uint64_t N,
-                                                        double* __restrict__ loss, int32_t* __restrict__ status) {
+                                                        const int64_t* __restrict__ labels, uint64_t n_labels,
+                                                        uint64_t N, double* __restrict__ loss,
+                                                        int32_t* __restrict__ status) {
     __shared__ double part[kLSumChunk];
     int mine_bad = 0;
-    for (uint64_t i = threadIdx.x; i < B; i += kLBlock) {
+    for (uint64_t i = threadIdx.x; i < n_labels; i += kLBlock) {
         const int64_t l = labels[i];
         mine_bad |= l < 0 || (uint64_t)l >= N;
     }
@@ -388,40 +399,49 @@ extern "C" int kf_dist_loss_scratch_bytes(uint64_t B, uint64_t* bytes) {
     return KF_OK;
 }
 
-extern "C" int kf_dist_loss(const float* d_y, uint64_t B, uint64_t E, const double* d_true, uint64_t N,
-                            const int64_t* d_labels, double* d_loss, float* d_grad, int32_t* d_status,
-                            void* d_scratch, uint64_t scratch_bytes, void* stream) {
-    if (B == 0) return kf_fail(KF_EINVAL, "kf_dist_loss: B == 0");
-    if (E == 0) return kf_fail(KF_EINVAL, "kf_dist_loss: E == 0");
+namespace kf {
+namespace {
+
+// both entries: `what` names the one called in its refusals
+int dist_loss_run(const char* what, const float* d_y, uint64_t B, uint64_t E, const double* d_true, uint64_t N,
+                  const int64_t* d_labels, uint64_t views, double eps, double* d_loss, float* d_grad,
+                  int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (B == 0) return kf_fail(KF_EINVAL, "%s: B == 0", what);
+    if (E == 0) return kf_fail(KF_EINVAL, "%s: E == 0", what);
+    if (views == 0) return kf_fail(KF_EINVAL, "%s: views == 0", what);
+    if (B % views != 0)
+        return kf_fail(KF_EINVAL, "%s: B = %llu rows are no multiple of views = %llu", what, (unsigned long long)B,
+                       (unsigned long long)views);
+    if (!(eps >= 0.0) || isinf(eps)) return kf_fail(KF_EINVAL, "%s: eps = %g: a finite value, not negative", what, eps);
     if (B > kLMaxB)
-        return kf_fail(KF_EINVAL, "kf_dist_loss: B = %llu: %llu rows at most per call", (unsigned long long)B,
+        return kf_fail(KF_EINVAL, "%s: B = %llu: %llu rows at most per call", what, (unsigned long long)B,
                        (unsigned long long)kLMaxB);
     if (E > kLMaxE)
-        return kf_fail(KF_EINVAL, "kf_dist_loss: E = %llu: 2^24 columns at most", (unsigned long long)E);
+        return kf_fail(KF_EINVAL, "%s: E = %llu: 2^24 columns at most", what, (unsigned long long)E);
     if (N == 0 || N >= (1ull << 30))
-        return kf_fail(KF_EINVAL, "kf_dist_loss: N = %llu: a matrix of 1 to 2^30 - 1 rows", (unsigned long long)N);
-    if (!d_y) return kf_fail(KF_EINVAL, "kf_dist_loss: null d_y");
-    if (!d_true) return kf_fail(KF_EINVAL, "kf_dist_loss: null d_true");
-    if (!d_labels) return kf_fail(KF_EINVAL, "kf_dist_loss: null d_labels");
-    if (!d_loss) return kf_fail(KF_EINVAL, "kf_dist_loss: null d_loss");
-    if (!d_status) return kf_fail(KF_EINVAL, "kf_dist_loss: null d_status");
-    if ((uintptr_t)d_y & 3) return kf_fail(KF_EINVAL, "kf_dist_loss: misaligned d_y (needs 4 bytes)");
-    if ((uintptr_t)d_true & 7) return kf_fail(KF_EINVAL, "kf_dist_loss: misaligned d_true (needs 8 bytes)");
-    if ((uintptr_t)d_labels & 7) return kf_fail(KF_EINVAL, "kf_dist_loss: misaligned d_labels (needs 8 bytes)");
-    if ((uintptr_t)d_loss & 7) return kf_fail(KF_EINVAL, "kf_dist_loss: misaligned d_loss (needs 8 bytes)");
-    if ((uintptr_t)d_grad & 3) return kf_fail(KF_EINVAL, "kf_dist_loss: misaligned d_grad (needs 4 bytes)");
-    if ((uintptr_t)d_status & 3) return kf_fail(KF_EINVAL, "kf_dist_loss: misaligned d_status (needs 4 bytes)");
-    if ((uintptr_t)d_scratch & 7) return kf_fail(KF_EINVAL, "kf_dist_loss: misaligned d_scratch (needs 8 bytes)");
+        return kf_fail(KF_EINVAL, "%s: N = %llu: a matrix of 1 to 2^30 - 1 rows", what, (unsigned long long)N);
+    if (!d_y) return kf_fail(KF_EINVAL, "%s: null d_y", what);
+    if (!d_true) return kf_fail(KF_EINVAL, "%s: null d_true", what);
+    if (!d_labels) return kf_fail(KF_EINVAL, "%s: null d_labels", what);
+    if (!d_loss) return kf_fail(KF_EINVAL, "%s: null d_loss", what);
+    if (!d_status) return kf_fail(KF_EINVAL, "%s: null d_status", what);
+    if ((uintptr_t)d_y & 3) return kf_fail(KF_EINVAL, "%s: misaligned d_y (needs 4 bytes)", what);
+    if ((uintptr_t)d_true & 7) return kf_fail(KF_EINVAL, "%s: misaligned d_true (needs 8 bytes)", what);
+    if ((uintptr_t)d_labels & 7) return kf_fail(KF_EINVAL, "%s: misaligned d_labels (needs 8 bytes)", what);
+    if ((uintptr_t)d_loss & 7) return kf_fail(KF_EINVAL, "%s: misaligned d_loss (needs 8 bytes)", what);
+    if ((uintptr_t)d_grad & 3) return kf_fail(KF_EINVAL, "%s: misaligned d_grad (needs 4 bytes)", what);
+    if ((uintptr_t)d_status & 3) return kf_fail(KF_EINVAL, "%s: misaligned d_status (needs 4 bytes)", what);
+    if ((uintptr_t)d_scratch & 7) return kf_fail(KF_EINVAL, "%s: misaligned d_scratch (needs 8 bytes)", what);
     const uint64_t need = scratch_need(B);
-    if (need && !d_scratch) return kf_fail(KF_EINVAL, "kf_dist_loss: null d_scratch");
+    if (need && !d_scratch) return kf_fail(KF_EINVAL, "%s: null d_scratch", what);
     if (scratch_bytes < need)
-        return kf_fail(KF_EINVAL, "kf_dist_loss: scratch of %llu bytes, %llu needed", (unsigned long long)scratch_bytes,
+        return kf_fail(KF_EINVAL, "%s: scratch of %llu bytes, %llu needed", what, (unsigned long long)scratch_bytes,
                        (unsigned long long)need);
     const hipStream_t s = (hipStream_t)stream;
     if (B <= (uint64_t)kLSmallB) {
         hipLaunchKernelGGL(dist_loss_small_kernel, dim3(1), dim3(kLSmallBlock), 0, s, d_y, (uint32_t)B, E, d_true, N,
-                           d_labels, d_loss, d_grad, d_status);
-        if (hipGetLastError() != hipSuccess) return kf_fail(KF_EHIP, "kf_dist_loss: launch failed");
+                           d_labels, (uint32_t)views, eps, d_loss, d_grad, d_status);
+        if (hipGetLastError() != hipSuccess) return kf_fail(KF_EHIP, "%s: launch failed", what);
         return KF_OK;
     }
     double* vT = (double*)d_scratch;
@@ -430,12 +450,30 @@ extern "C" int kf_dist_loss(const float* d_y, uint64_t B, uint64_t E, const doub
     const uint64_t tiles = (B + kLTile - 1) / kLTile, tiles_e = (E + kLTile - 1) / kLTile;
     hipLaunchKernelGGL(dist_kernel, dim3((uint32_t)(tiles * tiles)), dim3(kLBlock), 0, s, d_y, B, E, tiles, dc);
     hipLaunchKernelGGL(pair_kernel, dim3((uint32_t)((B * B + kLBlock - 1) / kLBlock)), dim3(kLBlock), 0, s, dc, vT, B,
-                       d_true, N, d_labels, d_grad != nullptr ? 1 : 0);
+                       d_true, N, d_labels, (uint32_t)views, eps, d_grad != nullptr ? 1 : 0);
     hipLaunchKernelGGL(rows_kernel, dim3((uint32_t)((B + 63) / 64)), dim3(64), 0, s, vT, B, rsum);
-    hipLaunchKernelGGL(total_kernel, dim3(1), dim3(kLBlock), 0, s, rsum, B, d_labels, N, d_loss, d_status);
+    hipLaunchKernelGGL(total_kernel, dim3(1), dim3(kLBlock), 0, s, rsum, B, d_labels, B / views, N, d_loss,
+                       d_status);
     if (d_grad != nullptr)
         hipLaunchKernelGGL(grad_kernel, dim3((uint32_t)(tiles * tiles_e)), dim3(kLBlock), 0, s, d_y, dc, B, E, tiles_e,
                            d_grad);
-    if (hipGetLastError() != hipSuccess) return kf_fail(KF_EHIP, "kf_dist_loss: launch failed");
+    if (hipGetLastError() != hipSuccess) return kf_fail(KF_EHIP, "%s: launch failed", what);
     return KF_OK;
+}
+
+}  // namespace
+}  // namespace kf
+
+extern "C" int kf_dist_loss(const float* d_y, uint64_t B, uint64_t E, const double* d_true, uint64_t N,
+                            const int64_t* d_labels, double* d_loss, float* d_grad, int32_t* d_status,
+                            void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return dist_loss_run("kf_dist_loss", d_y, B, E, d_true, N, d_labels, 1, 1e-6, d_loss, d_grad, d_status, d_scratch,
+                         scratch_bytes, stream);
+}
+
+extern "C" int kf_dist_loss_views(const float* d_y, uint64_t B, uint64_t E, const double* d_true, uint64_t N,
+                                  const int64_t* d_labels, uint64_t views, double eps, double* d_loss, float* d_grad,
+                                  int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return dist_loss_run("kf_dist_loss_views", d_y, B, E, d_true, N, d_labels, views, eps, d_loss, d_grad, d_status,
+                         d_scratch, scratch_bytes, stream);
 }

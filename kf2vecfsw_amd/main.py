@@ -1393,6 +1393,15 @@ def train_model_set(args) -> None:
     TR.train_model_set(args)
 
 
+def train_model_set_chunks(args) -> None:
+    """`train_model_set_chunks`: the distance model of every clade, trained on
+    random runs of its genomes' 10-kbp windows with kf_chunk_features and
+    kf_dist_loss_views (train_chunks.train_model_set_chunks_func;
+    kf2vec/main.py:934-957)."""
+    from . import train_chunks as TC
+    TC.train_model_set_chunks(args)
+
+
 def train_classifier(args) -> None:
     """`train_classifier`: the clade classifier of a library, trained on the
     device with kf_class_loss (train_classifier.train_classifier_model_func;
@@ -1438,6 +1447,8 @@ def build_parser() -> argparse.ArgumentParser:
                                             "train_classifier         Train classifier model based on backbone "
                                             "subtrees\n"
                                             "train_model_set          Trains individual models for each subtree\n"
+                                            "train_model_set_chunks   Trains individual models for each subtree "
+                                            "using chunked genomes as input\n"
                                             "classify                 Classifies query samples using previously "
                                             "trained classifier model\n"
                                             "query                    Query models\n"
@@ -1545,6 +1556,37 @@ def build_parser() -> argparse.ArgumentParser:
     pt.add_argument("-base_dim", type=int, default=4)
     pt.add_argument("-device", default=None, help="torch device (default: cuda)")
     pt.set_defaults(func=train_model_set)
+
+    ph = sub.add_parser("train_model_set_chunks",
+                        description="Trains individual models for each subtree using chunked genomes as input")
+    ph.add_argument("-input_dir", help="Directory of input k-mer frequencies for chunked assemblies "
+                                       "(dir of .kf files for chunked backbone species)")
+    ph.add_argument("-input_dir_fullgenomes", help="Directory of input k-mer frequencies for full assemblies "
+                                                   "(dir of .kf files for full backbone species)")
+    ph.add_argument("-true_dist", help="Directory of distamce matrices for backbone subtrees "
+                                       "(dir of *subtree_INDEX.di_mtrx files for backbone)")
+    ph.add_argument("-subtrees", help="Classification file with subtrees information obtained from divide_tree "
+                                      "command (a .subtrees format)")
+    ph.add_argument("-e", type=int, default=default_di_epochs,
+                    help="Number of epochs. Default: {}".format(default_di_epochs))
+    ph.add_argument("-hidden_sz", type=int, default=default_hidden_sz,
+                    help="Hidden size. Default: {}".format(default_hidden_sz))
+    ph.add_argument("-embed_sz", type=int, default=default_embed_sz,
+                    help="Embedding size. Default: {}".format(default_embed_sz))
+    ph.add_argument("-batch_sz", type=int, default=default_batch_sz,
+                    help="Batch size. Default: {}".format(default_batch_sz))
+    ph.add_argument("-lr", type=float, default=default_lr, help="Start learning rate. Default: {}".format(default_lr))
+    ph.add_argument("-lr_min", type=float, default=default_lr_min,
+                    help="Minimum learning rate. Default: {}".format(default_lr_min))
+    ph.add_argument("-lr_decay", type=float, default=default_lr_decay,
+                    help="Learning rate decay. Default: {}".format(default_lr_decay))
+    ph.add_argument("-clade", type=int, nargs="*", help="Clade number to train. Default: all")
+    ph.add_argument("-seed", type=int, default=default_seed, help="Random seed. Default: {}".format(default_seed))
+    ph.add_argument("-cap", action="store_true",
+                    help="Caps k-mer counts of every window at a maximum of 255")
+    ph.add_argument("-o", help="Model output path")
+    ph.add_argument("-device", default=None, help="torch device (default: cuda)")
+    ph.set_defaults(func=train_model_set_chunks)
 
     pq = sub.add_parser("query", description="Query models")
     pq.add_argument("-input_dir", help="Directory of input k-mer frequencies for assemblies or reads "

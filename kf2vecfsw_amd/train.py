@@ -75,7 +75,7 @@ def dist_loss_scratch_bytes(b: int) -> int:
 
 
 def dist_loss(y: torch.Tensor, table_values: torch.Tensor, labels: torch.Tensor, grad: bool = True,
-              stream: int | None = None):
+              stream: int | None = None, views: int = 1, eps: float = 1e-6):
     """Enqueue kf_dist_loss: y [B, E] float32, table_values [N, N] float64 (the
     clade's true distances, FloatTable.values) and labels [B] int64 (rows and
     columns of the table), all on one device.  Returns (loss float64 [], grad
@@ -83,11 +83,15 @@ def dist_loss(y: torch.Tensor, table_values: torch.Tensor, labels: torch.Tensor,
     weighted loss of the batch (cdist in the direct form, Loss.my_mse_loss) and
     its gradient with respect to y, bit for bit dist_loss_host.  status is 1,
     and the loss NaN, if a label is outside [0, N).  grad=False: the loss alone,
-    the same bits.  Nothing waits."""
+    the same bits.  Nothing waits.
+    With other views or eps than the defaults, kf_dist_loss_views: labels
+    [B / views], one per run of `views` rows (repeat_interleave), and the weight
+    1 / (T + eps) -- the chunk trainer's Loss_chunks at views=2, eps=1000."""
+    views = int(views)
     assert y.dim() == 2 and y.dtype == torch.float32
     assert table_values.dim() == 2 and table_values.shape[0] == table_values.shape[1]
     assert table_values.dtype == torch.float64 and labels.dtype == torch.int64 and labels.dim() == 1
-    assert labels.shape[0] == y.shape[0] and y.device == table_values.device == labels.device
+    assert views >= 1 and labels.shape[0] * views == y.shape[0] and y.device == table_values.device == labels.device
     y, table_values, labels = y.contiguous(), table_values.contiguous(), labels.contiguous()
     dev = y.device
     b, e = int(y.shape[0]), int(y.shape[1])
@@ -97,25 +101,32 @@ def dist_loss(y: torch.Tensor, table_values: torch.Tensor, labels: torch.Tensor,
     need = dist_loss_scratch_bytes(b) if b else 0
     scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev) if need else None
     s = C._stream_ptr(dev) if stream is None else stream
+    head = (y.data_ptr() if y.numel() else None, b, e, table_values.data_ptr(), int(table_values.shape[0]),
+            labels.data_ptr() if b else None)
+    tail = (loss.data_ptr(), g.data_ptr() if g is not None else None, status.data_ptr(),
+            scratch.data_ptr() if scratch is not None else None, 8 * scratch.numel() if scratch is not None else 0, s)
     with torch.cuda.device(dev):
-        N.check(N.lib().kf_dist_loss(y.data_ptr() if y.numel() else None, b, e, table_values.data_ptr(),
-                                     int(table_values.shape[0]), labels.data_ptr() if b else None, loss.data_ptr(),
-                                     g.data_ptr() if g is not None else None, status.data_ptr(),
-                                     scratch.data_ptr() if scratch is not None else None,
-                                     8 * scratch.numel() if scratch is not None else 0, s), "kf_dist_loss")
+        if views == 1 and eps == 1e-6:
+            N.check(N.lib().kf_dist_loss(*head, *tail), "kf_dist_loss")
+        else:
+            N.check(N.lib().kf_dist_loss_views(*head, views, float(eps), *tail), "kf_dist_loss_views")
     if stream is not None and scratch is not None:   # the scratch is the caller's stream's until the call is done
         scratch.record_stream(torch.cuda.ExternalStream(stream, device=dev))
     return loss, g, status
 
 
-def dist_loss_host(y, P, labels):
-    """The host statement of kf_dist_loss in numpy, the same operations in the
-    same order (include/kf2vec_gpu.h has the contract): returns (loss float64,
-    grad float32 [B, E]).  y [B, E] float32, P [N, N] float64, labels [B] inside
-    [0, N).  The tests compare the kernel with it; no product path calls it."""
+def dist_loss_host(y, P, labels, views: int = 1, eps: float = 1e-6):
+    """The host statement of kf_dist_loss and kf_dist_loss_views in numpy, the
+    same operations in the same order (include/kf2vec_gpu.h has the contract):
+    returns (loss float64, grad float32 [B, E]).  y [B, E] float32, P [N, N]
+    float64, labels [B / views] inside [0, N), row i's being labels[i // views].
+    The tests compare the kernel with it; no product path calls it."""
     y = np.ascontiguousarray(y, dtype=np.float32)
     P = np.ascontiguousarray(P, dtype=np.float64)
     lab = np.asarray(labels, dtype=np.int64).reshape(-1)
+    assert int(views) >= 1 and lab.shape[0] * int(views) == y.shape[0]
+    lab = lab[np.arange(y.shape[0]) // int(views)]
+    eps = float(eps)
     assert y.ndim == 2 and y.shape[0] == lab.shape[0] and y.shape[0] > 0 and y.shape[1] > 0
     assert P.ndim == 2 and P.shape[0] == P.shape[1] and lab.min() >= 0 and lab.max() < P.shape[0]
     b, e = y.shape
@@ -126,7 +137,7 @@ def dist_loss_host(y, P, labels):
             s = s + t * t
         d = np.sqrt(s)
         tt = P[np.ix_(lab, lab)]
-        w = 1.0 / (tt + 1e-6)
+        w = 1.0 / (tt + eps)
         r = np.sqrt(tt)
         u = d.astype(np.float64) - r
         v = (u * u) * w
@@ -152,8 +163,8 @@ class DistLoss(torch.autograd.Function):
     hands back the kernel's gradient times the upstream scalar."""
 
     @staticmethod
-    def forward(ctx, y, table_values, labels):
-        loss, g, status = dist_loss(y.detach(), table_values, labels, grad=True)
+    def forward(ctx, y, table_values, labels, views=1, eps=1e-6):
+        loss, g, status = dist_loss(y.detach(), table_values, labels, grad=True, views=views, eps=eps)
         ctx.save_for_backward(g)
         ctx.mark_non_differentiable(status)
         return loss, status
@@ -161,12 +172,13 @@ class DistLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss, _grad_status):
         (g,) = ctx.saved_tensors
-        return g * grad_loss.to(torch.float32), None, None
+        return g * grad_loss.to(torch.float32), None, None, None, None
 
 
-def dist_loss_fn(y: torch.Tensor, table_values: torch.Tensor, labels: torch.Tensor):
+def dist_loss_fn(y: torch.Tensor, table_values: torch.Tensor, labels: torch.Tensor, views: int = 1,
+                 eps: float = 1e-6):
     """(loss, status) of the batch, differentiable with respect to y."""
-    return DistLoss.apply(y, table_values, labels)
+    return DistLoss.apply(y, table_values, labels, views, eps)
 
 
 # ---------------------------------------------------------------------------
