@@ -399,6 +399,37 @@ int kf_chunk_features(const void* d_counts, int count_bytes, uint64_t n_rows, ui
                       uint32_t cap, double scaler, void* d_out, int out_bytes,
                       uint32_t* d_status, void* d_work, uint64_t work_bytes, void* stream);
 
+/* ---- the same samples from a store of one byte per count (the reference's -cap:
+ * utils.my_read_csv_chunk_capped keeps min(count, 255) as uint8 to halve the memory
+ * of the whole library's window rows):
+ *   d_counts         : n_rows x nbins u8 counts, row-major, already capped
+ * and every other argument as kf_chunk_features', without count_bytes and cap.
+ * For every table, scaler and out_bytes, d_out equals kf_chunk_features' on the
+ * same values widened to u16 with cap = UINT32_MAX, bit for bit; so it also equals
+ * kf_chunk_features with cap = 255 on the uncapped u16 rows these were made from
+ * (kf_rows_cap8).  The sums are exact for any d_n; T == 0, the table check
+ * (*d_status = 2, no byte written), n_samples == 0, KF_EINVAL and KF_ERANGE (the
+ * messages start with "kf_chunk_features8: "; d_counts needs no alignment) and the
+ * scratch (kf_chunk_features_scratch_bytes) are kf_chunk_features'.
+ * The same kernels over 16 columns per 16-byte load, where nbins is a multiple of
+ * 16 and d_counts and d_out are 16-byte aligned: two loads per row and thread,
+ * eight rows in flight; the bytes are added two to a 32-bit word and these 16-bit
+ * partial sums folded into the 64-bit sums every 256 rows, before one can wrap.
+ * Any other call takes the scalar path with the same result.  At most one memset
+ * and two launches, as kf_chunk_features. */
+int kf_chunk_features8(const uint8_t* d_counts, uint64_t n_rows, uint64_t nbins,
+                       const uint64_t* d_lo, const uint64_t* d_n, int32_t n_samples,
+                       double scaler, void* d_out, int out_bytes,
+                       uint32_t* d_status, void* d_work, uint64_t work_bytes, void* stream);
+
+/* d_dst[i] = min(d_src[i], 255) for i < n: u16 window rows to the u8 rows of
+ * kf_chunk_features8.  One streaming launch, 16-byte loads and stores where the
+ * pointers allow (d_dst may have any alignment: the elements up to its next
+ * 16-byte line and those behind the last whole group go one by one).  n == 0 is
+ * a no-op.  KF_EINVAL for a null pointer or an odd d_src.  The arrays must not
+ * overlap.  Asynchronous on `stream`, no allocation, no host synchronisation. */
+int kf_rows_cap8(const uint16_t* d_src, uint64_t n, uint8_t* d_dst, void* stream);
+
 /* ---- get_chunks `.kf` text parsed on the device into the uint16 window rows the
  * chunk trainers hold after my_read_csv_chunk (kf2vec/utils.py:402-405: pandas
  * read_csv with dtype=uint16), for many files or pieces of files per call:

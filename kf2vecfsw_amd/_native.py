@@ -71,6 +71,8 @@ SIGNATURES = {
     "kf_chunk_features_scratch_bytes": (_u64, [_i32]),
     "kf_chunk_features": (_int, [_vp, _int, _u64, _u64, _vp, _vp, _i32, _u32, ctypes.c_double, _vp, _int, _vp, _vp, _u64,
                                  _vp]),
+    "kf_chunk_features8": (_int, [_vp, _u64, _u64, _vp, _vp, _i32, ctypes.c_double, _vp, _int, _vp, _vp, _u64, _vp]),
+    "kf_rows_cap8": (_int, [_vp, _u64, _vp, _vp]),
     "kf_parse_kf_scratch_bytes": (_u64, [_u64, _i32, _u64]),
     "kf_parse_kf_rows": (_int, [_vp, _vp, _i32, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
     "kf_parse_kf_floats_scratch_bytes": (_u64, [_u64, _i32, _u64]),

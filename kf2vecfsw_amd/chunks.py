@@ -628,7 +628,9 @@ class ChunkStore:
     """A directory's window count rows on the device, as train_model_set_chunks
     holds them after my_read_csv_chunk (kf2vec/utils.py:402-405): genome g's rows
     are counts[row0[g]: row0[g + 1]]."""
-    counts: torch.Tensor    # int16 [W, nbins] holding uint16 bit patterns, the kept genomes' rows back to back
+    # int16 [W, nbins] holding uint16 bit patterns, the kept genomes' rows back to back; or uint8 [W, nbins], each
+    # count as min(count, 255) (chunk_store_from_kf(cap8=True): utils.my_read_csv_chunk_capped's store)
+    counts: torch.Tensor
     row0: np.ndarray        # int64 [G + 1], host
     samples: list           # G sample names
     excluded: dict          # sample name -> "none" (no contig >= 10 kbp) or "few" (windows)
@@ -636,19 +638,21 @@ class ChunkStore:
 
     @classmethod
     def from_host(cls, rows_per_genome, samples, k: int, device="cuda") -> "ChunkStore":
-        """A store of uint16 [windows, nbins] arrays, one per genome (the parsed rows of its .kf file)."""
+        """A store of uint16 [windows, nbins] arrays, one per genome (the parsed rows of its .kf file); or of
+        uint8 arrays, all of them (rows capped at 255), which make a uint8 store."""
         from .counter import num_bins
         nb = num_bins(k)
         rows = [np.asarray(r) for r in rows_per_genome]
         if len(rows) != len(samples):
             raise ValueError("ChunkStore.from_host: {} genomes but {} sample names".format(len(rows), len(samples)))
+        width = np.uint8 if rows and all(r.dtype == np.uint8 for r in rows) else np.uint16
         for r, name in zip(rows, samples):
-            if r.dtype != np.uint16 or r.ndim != 2 or r.shape[1] != nb:
-                raise ValueError("ChunkStore.from_host: {}: rows must be uint16 [windows, {}] at k={}, got {} {}".format(
-                    name, nb, k, r.dtype, r.shape))
+            if r.dtype != width or r.ndim != 2 or r.shape[1] != nb:
+                raise ValueError("ChunkStore.from_host: {}: rows must be uint16 (or all uint8) [windows, {}] at k={}, "
+                                 "got {} {}".format(name, nb, k, r.dtype, r.shape))
         row0 = np.cumsum([0] + [r.shape[0] for r in rows]).astype(np.int64)
-        host = np.concatenate(rows) if rows else np.zeros((0, nb), np.uint16)
-        counts = torch.from_numpy(np.ascontiguousarray(host).view(np.int16)).to(torch.device(device))
+        host = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, nb), np.uint16))
+        counts = torch.from_numpy(host if width == np.uint8 else host.view(np.int16)).to(torch.device(device))
         return cls(counts, row0, list(samples), {}, k)
 
     def batch(self, idx, rng, scaler: float = 1e4, cap: int | None = None, dtype: torch.dtype = torch.float32):
@@ -844,7 +848,8 @@ def kf_line_pieces(path: str, piece: int | None = None, start: int = 0) -> list[
     return [(c, cuts[i + 1] if i + 1 < len(cuts) else size) for i, c in enumerate(cuts)]
 
 
-def chunk_store_from_kf(kf_dir: str, k: int, device="cuda", samples=None, batch_gb: float = 1.0, p=None) -> ChunkStore:
+def chunk_store_from_kf(kf_dir: str, k: int, device="cuda", samples=None, batch_gb: float = 1.0, p=None,
+                        cap8: bool = False) -> ChunkStore:
     """The store of a directory of get_chunks `.kf` files (this tool's or the
     reference's), as train_model_set_chunks holds them after my_read_csv_chunk
     under mp.Pool (kf2vec/train_model_set_chunks.py:251-264), with the text parsed
@@ -861,9 +866,14 @@ def chunk_store_from_kf(kf_dir: str, k: int, device="cuda", samples=None, batch_
     and parsed there, and one small copy per batch brings its units' row counts
     (and any refusal: a ValueError naming file, row and column) back.  The
     batches' rows are joined by one torch.cat at the end, so the peak device
-    memory is the store plus its parts (twice the store) plus one batch."""
+    memory is the store plus its parts (twice the store) plus one batch.
+
+    cap8=True: the store of utils.my_read_csv_chunk_capped (the trainers' -cap),
+    every count as min(count, 255) in one byte: each batch's parsed rows go
+    through kf_rows_cap8 and only the uint8 rows are kept, so the parts, their
+    join and `counts` (torch.uint8) are half the bytes."""
     from . import main as M
-    from .counter import num_bins, pack_ranges, parse_kf_rows, parsed_to_host
+    from .counter import num_bins, pack_ranges, parse_kf_rows, parsed_to_host, rows_cap8
     if k not in M.supported_k:
         raise ValueError("k={} has no vocabulary: supported k are {}..{}".format(
             k, M.supported_k.start, M.supported_k.stop - 1))
@@ -908,11 +918,13 @@ def chunk_store_from_kf(kf_dir: str, k: int, device="cuda", samples=None, batch_
             row0 = parsed_to_host(unit_row0, status, names, [file_rows[units[i][0]] for i in b], first)
             for x, i in enumerate(b):
                 file_rows[units[i][0]] += int(row0[x + 1] - row0[x])
-            parts.append(rows[: int(row0[-1])].clone())   # the batch's rows without the slack of its cap
+            rows = rows[: int(row0[-1])]                   # the batch's rows without the slack of its cap
+            parts.append(rows_cap8(rows) if cap8 else rows.clone())
             del rows, d_bytes, hb
     kept = [fi for fi in range(len(paths)) if file_rows[fi] > 0]
     excluded = {samples[fi]: "none" for fi in range(len(paths)) if file_rows[fi] == 0}
     row0 = np.cumsum([0] + [file_rows[fi] for fi in kept]).astype(np.int64)
-    counts = torch.cat(parts) if parts else torch.zeros((0, nbins), dtype=torch.int16, device=device)
+    counts = torch.cat(parts) if parts else torch.zeros((0, nbins), dtype=torch.uint8 if cap8 else torch.int16,
+                                                        device=device)
     del parts
     return ChunkStore(counts.contiguous(), row0, [samples[fi] for fi in kept], excluded, k)

@@ -635,7 +635,12 @@ def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | 
     chunks.range_features_host states it in numpy, bit for bit.
 
     counts: contiguous [n_rows, nbins] on the device, int16 holding uint16 bit
-    patterns (ChunkStore.counts) or int32 holding uint32 (KmerCounter.count).
+    patterns (ChunkStore.counts) or int32 holding uint32 (KmerCounter.count); or
+    uint8, the rows of a store that was capped at 255 as it was read
+    (chunks.chunk_store_from_kf(cap8=True), rows_cap8), which go through
+    kf_chunk_features8: `cap` must then be None or at least 255 (a ValueError
+    otherwise), and the result is this function's with cap=255 on the uint16
+    rows the store was made from, bit for bit.
     lo, n: host arrays (one staged pinned copy), or int64 tensors on the device.
     The device checks the table; its status word is read back here (the call's
     one synchronisation) and a sample outside [0, n_rows] raises N.NativeError
@@ -643,8 +648,12 @@ def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | 
     and (out, status) come back, status the int32 [1] word on the device, not
     zero where a sample lay outside -- the caller reads it with its own next
     read (the chunk trainer: once per epoch)."""
-    assert counts.dtype in (torch.int16, torch.int32) and counts.dim() == 2 and counts.is_contiguous()
+    assert counts.dtype in (torch.uint8, torch.int16, torch.int32) and counts.dim() == 2 and counts.is_contiguous()
     assert dtype in (torch.float32, torch.float64)
+    rows8 = counts.dtype == torch.uint8
+    if rows8 and cap is not None and int(cap) < 255:
+        raise ValueError("chunk_features: cap={} with uint8 rows, which are capped at 255 already: a lower cap needs "
+                         "the uint16 rows".format(cap))
     dev = counts.device
     if isinstance(lo, torch.Tensor) and lo.is_cuda:
         assert isinstance(n, torch.Tensor) and n.device == lo.device == dev and lo.shape == n.shape
@@ -667,10 +676,16 @@ def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | 
     work = torch.empty(need // 8, dtype=torch.int64, device=dev)
     s = _stream_ptr(dev) if stream is None else stream
     with torch.cuda.device(dev):
-        N.check(N.lib().kf_chunk_features(
-            counts.data_ptr() if counts.shape[0] else None, counts.element_size(), counts.shape[0], nbins,
-            d_lo.data_ptr(), d_n.data_ptr(), ns, 0xFFFFFFFF if cap is None else int(cap), float(scaler),
-            out.data_ptr(), out.element_size(), status.data_ptr(), work.data_ptr(), need, s), "kf_chunk_features")
+        if rows8:
+            N.check(N.lib().kf_chunk_features8(
+                counts.data_ptr() if counts.shape[0] else None, counts.shape[0], nbins, d_lo.data_ptr(), d_n.data_ptr(),
+                ns, float(scaler), out.data_ptr(), out.element_size(), status.data_ptr(), work.data_ptr(), need, s),
+                "kf_chunk_features8")
+        else:
+            N.check(N.lib().kf_chunk_features(
+                counts.data_ptr() if counts.shape[0] else None, counts.element_size(), counts.shape[0], nbins,
+                d_lo.data_ptr(), d_n.data_ptr(), ns, 0xFFFFFFFF if cap is None else int(cap), float(scaler),
+                out.data_ptr(), out.element_size(), status.data_ptr(), work.data_ptr(), need, s), "kf_chunk_features")
     if not check:
         if stream is not None:   # the work table is the caller's stream's until the call is done
             work.record_stream(torch.cuda.ExternalStream(stream, device=dev))
@@ -679,6 +694,25 @@ def chunk_features(counts: torch.Tensor, lo, n, scaler: float = 1.0, cap: int | 
         torch.cuda.synchronize(dev)
     if int(status.item()) != 0:
         raise N.NativeError("kf_chunk_features: a sample's rows lie outside the count matrix (nothing was written)")
+    return out
+
+
+def rows_cap8(rows: torch.Tensor, out: torch.Tensor | None = None, stream: int | None = None) -> torch.Tensor:
+    """Enqueue kf_rows_cap8: the uint8 tensor min(rows, 255) of `rows`' shape for
+    int16 rows holding uint16 bit patterns (torch has no unsigned 16-bit clamp),
+    contiguous and on the device -- what utils.my_read_csv_chunk_capped keeps of
+    a count.  `out`: a contiguous uint8 tensor of that many elements to write
+    to.  Nothing waits."""
+    assert rows.dtype == torch.int16 and rows.is_contiguous()
+    if out is None:
+        out = torch.empty(rows.shape, dtype=torch.uint8, device=rows.device)
+    assert out.dtype == torch.uint8 and out.numel() == rows.numel() and out.is_contiguous()
+    assert out.device == rows.device
+    n = rows.numel()
+    if n:
+        s = _stream_ptr(rows.device) if stream is None else stream
+        with torch.cuda.device(rows.device):
+            N.check(N.lib().kf_rows_cap8(rows.data_ptr(), n, out.data_ptr(), s), "kf_rows_cap8")
     return out
 
 

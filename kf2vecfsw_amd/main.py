@@ -1410,6 +1410,16 @@ def train_classifier(args) -> None:
     TC.train_classifier(args)
 
 
+def train_classifier_chunks(args) -> None:
+    """`train_classifier_chunks`: the clade classifier of a library, trained on
+    random runs of its genomes' 10-kbp windows with kf_chunk_features (under
+    -cap kf_chunk_features8 over a uint8 store) and kf_class_loss
+    (train_classifier_chunks.train_classifier_model_chunks_func;
+    kf2vec/main.py:960-967)."""
+    from . import train_classifier_chunks as TCC
+    TCC.train_classifier_chunks(args)
+
+
 def process_query_data(args) -> None:
     """`process_query_data`: get_frequencies, classify and query one after
     another in this process, with the reference's banner lines and its rewiring
@@ -1446,6 +1456,8 @@ def build_parser() -> argparse.ArgumentParser:
                                             "get_chunks               Extract chunks from reference assemblies\n"
                                             "train_classifier         Train classifier model based on backbone "
                                             "subtrees\n"
+                                            "train_classifier_chunks  Train classifier model based on backbone "
+                                            "subtrees (genomes split into chunks)\n"
                                             "train_model_set          Trains individual models for each subtree\n"
                                             "train_model_set_chunks   Trains individual models for each subtree "
                                             "using chunked genomes as input\n"
@@ -1523,6 +1535,34 @@ def build_parser() -> argparse.ArgumentParser:
     pa.add_argument("-o", help="Model output path")
     pa.add_argument("-device", default=None, help="torch device (default: cuda)")
     pa.set_defaults(func=train_classifier)
+
+    pb = sub.add_parser("train_classifier_chunks",
+                        description="Train classifier model based on backbone subtrees (genomes split into chunks)")
+    pb.add_argument("-input_dir", help="Directory of input k-mer frequencies for assemblies or reads "
+                                       "(dir of .kf files for backbone)")
+    pb.add_argument("-input_dir_fullgenomes", help="Directory of input k-mer frequencies for full assemblies "
+                                                   "(dir of .kf files for full backbone species)")
+    pb.add_argument("-subtrees", help="Classification file with subtrees information obtained from divide_tree "
+                                      "command (a .subtrees format)")
+    pb.add_argument("-e", type=int, default=default_cl_epochs,
+                    help="Number of epochs. Default: {}".format(default_cl_epochs))
+    pb.add_argument("-hidden_sz", type=int, default=default_hidden_sz,
+                    help="Hidden size. Default: {}".format(default_hidden_sz))
+    pb.add_argument("-batch_sz", type=int, default=default_batch_sz,
+                    help="Batch size. Default: {}".format(default_batch_sz))
+    pb.add_argument("-lr", type=float, default=default_lr, help="Start learning rate. Default: {}".format(default_lr))
+    pb.add_argument("-lr_min", type=float, default=default_lr_min,
+                    help="Minimum learning rate. Default: {}".format(default_lr_min))
+    pb.add_argument("-lr_decay", type=float, default=default_lr_decay,
+                    help="Learning rate decay. Default: {}".format(default_lr_decay))
+    pb.add_argument("-seed", type=int, default=default_seed, help="Random seed. Default: {}".format(default_seed))
+    pb.add_argument("-mask", action="store_true", help=argparse.SUPPRESS)
+    pb.add_argument("-cap", action="store_true",
+                    help="Reduces memory consumption for input dataset (caps k-mer counts at a maximum of 255, kept "
+                         "as one byte each)")
+    pb.add_argument("-o", help="Model output path")
+    pb.add_argument("-device", default=None, help="torch device (default: cuda)")
+    pb.set_defaults(func=train_classifier_chunks)
 
     pt = sub.add_parser("train_model_set", description="Trains individual models for each subtree")
     pt.add_argument("-input_dir", help="Directory of input k-mer frequencies for assemblies or reads "

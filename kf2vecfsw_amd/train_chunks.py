@@ -99,7 +99,7 @@ def _row0_device(store) -> torch.Tensor:
 
 def epoch_batches(store, rows: torch.Tensor, perm: torch.Tensor, plan, gen: torch.Generator,
                   scaler: float = features_scaler, cap: int | None = None, budget: int = FEATURE_SLAB_BYTES,
-                  status: torch.Tensor | None = None):
+                  status: torch.Tensor | None = None, views: int = VIEWS):
     """An epoch's batches: yields (Z [2 b, nbins] float32, labels int64 [b]) on the
     store's device for every (start, end) of `plan` over the items rows[perm]
     (`rows`: the store's genome of every training item, which is also its row of
@@ -112,23 +112,25 @@ def epoch_batches(store, rows: torch.Tensor, perm: torch.Tensor, plan, gen: torc
     the budget.  Nothing waits for the device: every slab's status word is added
     to `status` (a one-element tensor on the device, for the caller's own read);
     with status=None the words are read here after the last batch, and a run
-    outside the store raises N.NativeError."""
+    outside the store raises N.NativeError.  views: the runs per item (2 here;
+    1 for Dataset_chunks_1row, the chunk classifier's: Z is then [b, nbins])."""
+    views = int(views)
     counts = store.counts
     row0 = _row0_device(store)
     items = rows.index_select(0, perm)
     first = row0.index_select(0, items)
     c = row0.index_select(0, items + 1) - first
-    lo, n = draw_runs(c, gen, VIEWS)
+    lo, n = draw_runs(c, gen, views)
     lo = (lo + first.reshape(-1, 1)).reshape(-1).contiguous()
     n = n.reshape(-1).contiguous()
     folded = torch.zeros(1, dtype=torch.int64, device=counts.device) if status is None else status
-    for b0, b1 in slab_plan(plan, 4 * counts.shape[1], budget):
+    for b0, b1 in slab_plan(plan, 4 * counts.shape[1], budget, views):
         a, e = plan[b0][0], plan[b1 - 1][1]
-        z, st = C.chunk_features(counts, lo[VIEWS * a: VIEWS * e], n[VIEWS * a: VIEWS * e], scaler, cap, torch.float32,
+        z, st = C.chunk_features(counts, lo[views * a: views * e], n[views * a: views * e], scaler, cap, torch.float32,
                                  check=False)
         folded.add_(st.to(folded.dtype))
         for s, t in plan[b0:b1]:
-            yield z[VIEWS * (s - a): VIEWS * (t - a)], items[s:t]
+            yield z[views * (s - a): views * (t - a)], items[s:t]
         del z
     if status is None and int(folded.item()) != 0:
         raise N.NativeError("kf_chunk_features: a run's rows lie outside the count matrix")
